@@ -183,7 +183,7 @@ def test_rccl_process_group_of_one_rank_runs_the_collectives(tmp_path):
 
 
 def test_bench_two_ranks_completes():
-    """Plain `python bench.py --gpus 2` (bench.py starts its own one-process-per-GPU job as a child process; both ranks on
+    """`python bench.py --gpus 2 --full` (bench.py starts its own one-process-per-GPU job as a child process; both ranks on
     cuda:0 over gloo here, VG_BENCH_ONE_DEVICE=1): the driver's multi-GPU contract -- barrier-bracketed timed steps, MAX over
     ranks, the per-launch timing step on EVERY rank (it contains the all-reduces: on rank 0 alone it dead-locked), one JSON
     line from rank 0, the child's return code relayed."""
@@ -191,7 +191,7 @@ def test_bench_two_ranks_completes():
     env = dict(os.environ, VG_BENCH_ONE_DEVICE='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--size', '32']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--size', '32', '--full']
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = r.stdout.decode()
     assert r.returncode == 0, out[-3000:]

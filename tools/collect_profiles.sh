@@ -12,7 +12,7 @@ VG_LANES=0 VG_SIDE_STREAM=0 VG_OPT_STREAM=0 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CY
 cd $R
 python3 tools/hbm_pmc.py $O/fetch $O/write $O/hbm_pmc.json > $O/hbm_pmc.log 2>&1
 cp $O/hbm_pmc.json $R/profiles/${tag}_hbm_pmc.json     # the bench line below quotes it (same kernel sources: hash-stamped)
-python3 $R/bench.py --steps 20 --warmup 5 --dump-kernels $O/bench_kernels.json > $O/bench_line.json 2> $O/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 --dump-kernels $O/bench_kernels.json > $O/bench_line.json 2> $O/bench.err
 python3 tools/mfma_pmc.py $O/mfma $O/mfma_pmc.json > $O/mfma_pmc.log 2>&1
 python3 tools/roofline_by_kernel.py $O/bench_kernels.json $O/stats 7 $O/fetch $O/write 2 $O/roofline_by_kernel.json > $O/roofline_by_kernel.txt 2>&1
 cp $(find $O/stats -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
