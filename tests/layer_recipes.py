@@ -32,6 +32,11 @@ NEEDED = ('128^3 B1', '64^3 B2', '128x128x64 B2')
 def enumerate_config(dims, B, precision='bf16'):
     """-> [(kind, layer name, variant, recipe)] of one train step's conv launches (one generator: a forward application and the
     backward sweep over both applications; one discriminator with its two backward sweeps: the others repeat the same calls)."""
+    return walk_config(dims, B, precision)[0]
+
+
+def walk_config(dims, B, precision='bf16'):
+    """-> (enumerate_config's list, [(entry point, regime)] of the same walk's non-convolution calls: ops.DryRun.calls)."""
     from van_gan_amd import ops
     from van_gan_amd.nets import ParamStore, PatchGAN, ResUNet, disc_param_specs, gen_param_specs
     dt = torch.bfloat16 if precision == 'bf16' else torch.float32
@@ -48,11 +53,11 @@ def enumerate_config(dims, B, precision='bf16'):
         ar.pair_begin('g', 0)
         ctx = G.forward(ar, x2[:B], y)
         ar.pair_end()
-        n0 = len(dry.records)
+        n0, c0 = len(dry.records), len(dry.calls)
         ar.pair_begin('g', 1)
         G.forward(ar, x2[B:], yb)
         ar.pair_end()
-        del dry.records[n0:]; del dry.recipes[n0:]
+        del dry.records[n0:]; del dry.recipes[n0:]; del dry.calls[c0:]
         G.backward(ar, pair_ctx(ar, ctx, x2, (y, yb), G.lv[0]), x2)
         lg = ar.alloc((2 * B,) + tuple(n // 8 for n in dims) + (1,), torch.float32)
         noise = {k: torch.empty(shp, dtype=torch.bfloat16) for k, shp in D.noise_shapes(2 * B).items()}
@@ -61,7 +66,7 @@ def enumerate_config(dims, B, precision='bf16'):
         # the step's discriminator backward: ONE sweep over [d critic loss (2B); d generator loss (B)] (PatchGAN.backward_both)
         lg3 = ar.alloc((3 * B,) + tuple(n // 8 for n in dims) + (1,), torch.float32)
         D.backward_both(ar, dctx, lg3, B, ar.alloc((B,) + dims + (1,), torch.float32))
-    return [(k, n, v, r) for (k, n, v), r in zip(dry.records, dry.recipes)]
+    return [(k, n, v, r) for (k, n, v), r in zip(dry.records, dry.recipes)], list(dry.calls)
 
 
 def enumerate_resnet(dims, N):

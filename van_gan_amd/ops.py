@@ -63,7 +63,40 @@ class DryRun:
     vg_conv3d / vg_conv3d_wgrad run their complete host-side dispatch WITHOUT launching and report the kernel variant they
     selected (vg_conv3d_variant / vg_conv3d_wgrad_variant).  Works on CPU tensors: the schedules of nets.py can be walked on
     a box without a GPU to list the kernels a configuration would run (tests/test_variant_coverage.py).
-    records: [(kind, layer name, variant string)], kind in fwd / dgrad / wgrad."""
+    records: [(kind, layer name, variant string)], kind in fwd / dgrad / wgrad.
+    calls: [(entry point, regime)] of the non-convolution entry points in _CALLS -- the descriptor's shape-level fields (no
+    pointers: a pointer only says whether it is set), enough to rebuild the call with random contents."""
+
+    _CALLS = ('vg_actnorm_bwd', 'vg_actnorm_bwd_stats', 'vg_actnorm_bwd_apply', 'vg_actnorm_bwd_apply2', 'vg_concat_bwd', 'vg_affine_add',
+              'vg_in_finalize', 'vg_stem_short_fwd', 'vg_stem_short_bwd', 'vg_tanh_bwd')
+    _ANB_FIELDS = ('N', 'D', 'H', 'W', 'C', 'g_padded', 'f32', 'x_f32', 'c_x0', 'x0_shift', 'act', 'norm', 'alias_n0', 'alias_shift',
+                   'pgrad_n', 'dx_f32', 'accumulate', 'dx_cstride', 'dx_coff')
+
+    @classmethod
+    def anb_regime(cls, d: ActNormBwdDesc) -> tuple:
+        """Shape-level regime of an InstanceNorm-backward descriptor: its fields, and which optional operands are set."""
+        return tuple((f, int(getattr(d, f))) for f in cls._ANB_FIELDS) + \
+            tuple(('has_' + f, int(bool(getattr(d, f)))) for f in ('x', 'x1', 'scale', 'mult', 'dgamma'))
+
+    def _call(self, name, a) -> tuple:
+        if name == 'vg_actnorm_bwd_apply2':
+            return (('job1', self.anb_regime(a[0]._obj)), ('job2', self.anb_regime(a[1]._obj)))
+        if name.startswith('vg_actnorm_bwd'):
+            return self.anb_regime(a[0]._obj)
+        if name == 'vg_concat_bwd':
+            return (('N', a[1]), ('D', a[2]), ('H', a[3]), ('W', a[4]), ('Cu', a[5]), ('Cs', a[6]), ('has_dskip', int(bool(a[8]))),
+                    ('f32', a[9]), ('acc', a[10]))
+        if name == 'vg_affine_add':
+            return (('a_act', a[3]), ('N', a[7]), ('S', a[8]), ('C', a[9]), ('out_f32', a[11]))
+        if name == 'vg_in_finalize':
+            return (('c0', a[1]), ('count0', a[2]), ('has_sums1', int(bool(a[3]))), ('c1', a[4]), ('count1', a[5]), ('has_gamma', int(bool(a[6]))),
+                    ('has_mult', int(bool(a[8]))), ('N', a[9]))
+        if name == 'vg_stem_short_fwd':
+            return (('N', a[1]), ('S', a[2]), ('C', a[3]), ('round16', a[8]), ('G', a[12]))
+        if name == 'vg_stem_short_bwd':
+            return (('g_f32', a[1]), ('N', a[3]), ('S', a[4]), ('C', a[5]), ('round16', a[9]), ('has_dgamma', int(bool(a[11]))), ('G', a[14]))
+        assert name == 'vg_tanh_bwd'
+        return (('n', a[3]),)
 
     _PASS = ('vg_conv3d_dma_bn', 'vg_conv3d_scratch_bytes', 'vg_conv3d_thin_np', 'vg_conv3d_plan', 'vg_packed_ktot', 'vg_packed_rows', 'vg_conv3d_lds_bytes', 'vg_status_string', 'vg_set_tuning',
              'vg_stem_short_bwd_workgroups', 'vg_stem_short_fwd_workgroups')
@@ -73,11 +106,17 @@ class DryRun:
         self.tag = ('?', '?')
         self.recipe = None          # how to rebuild the call that is being recorded (ConvLayer fills it in)
         self.recipes = []           # parallel to records
+        self.calls = []
 
     def __getattr__(self, name):            # stands in for `lib`
         real = _lib.lib
         if name in self._PASS:
             return getattr(real, name)
+        if name in self._CALLS:
+            def call(*a):
+                self.calls.append((name, self._call(name, a)))
+                return 0
+            return call
         if name == 'vg_conv3d':
             def conv(dref, _stream):
                 buf = C.create_string_buffer(512)
@@ -891,7 +930,10 @@ class ConvLayer:
         if DRY is not None:
             DRY.tag = ('fwd', self.name)
             DRY.recipe = dict(kind='fwd', layer=self.ctor, src=src.recipe(), res=res is not None, res_c1=bool(res_c1), tanh=bool(tanh),
-                              sums=sums is not None, out_f32=out.dtype == torch.float32)
+                              sums=sums is not None, out_f32=out.dtype == torch.float32,
+                              fin=None if fin is None else dict(count=fin.count, jobs=tuple(
+                                  dict(c_off=q.c_off, c_tot=q.c_tot, gamma=bool(q.gamma), beta=bool(q.beta), mult=bool(q.mult))
+                                  for q in fin.job[:fin.njobs])))
         e0 = PROF.begin() if PROF is not None else None
         check(lib.vg_conv3d(C.byref(d), s_), 'vg_conv3d ' + self.name)
         if e0 is not None:
