@@ -50,7 +50,7 @@ int vg_version(void);
  * post_training.py:38-39 / custom_callback.py:174-175).  Every "bf16" buffer of this header holds that format. */
 int vg_storage16(void);
 /* sizeof() of the descriptor structs as THIS library was compiled (which: 0 vg_conv_desc, 1 vg_actnorm_bwd_desc,
- * 2 vg_pack_item, 3 vg_fin_desc; else VG_EINVAL): a binding that mirrors the structs by hand checks its layout at load time. */
+ * 2 vg_pack_item, 3 vg_fin_desc, 4 vg_sn_item; else VG_EINVAL): a binding that mirrors the structs by hand checks its layout at load time. */
 int vg_abi_sizeof(int which);
 
 /* ---------------------------------------------------------------------------------------------
@@ -464,6 +464,38 @@ int vg_divide_crop(const float* pred, const float* cnt, int X, int Y, int Z, int
 int vg_adam_clip(float* w, const float* g, float* m, float* v, const int64_t* seg_off_dev, int T,
                  int64_t total, float* norms, float lr_t, float beta1, float beta2, float eps,
                  float clipnorm, float grad_scale, vg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Spectral normalisation of the discriminator's wrapped convolution kernels (get_discriminator(use_SN=True), discriminator.py:16,54-61,
+ * 86,100; building_blocks.py:172-180 -- tfa.layers.SpectralNormalization with power_iterations = 1), multi-tensor: one call serves every
+ * wrapped kernel of a network from a device table.  TP (TensorFlow Addons, restated): w is the fp32 master kernel in Keras layout viewed
+ * as [K = k^3 * Cin][Cout], u [Cout] the stored power-iteration vector; one projection is
+ *   l2n(x) = x * rsqrt(max(sum(x * x), 1e-12));  v = l2n(u w^T);  u' = l2n(v w);  sigma = (v w) . u';  u <- u';  w <- w / sigma   (in place).
+ * n_proj (1 .. VG_SN_MAX_PROJ) projections are applied back to back (the reference calls a discriminator twice per training step); w is
+ * read n_proj + 1 times and written once.  state[VG_SN_STATE]: [p] = sigma of projection p of this call, [VG_SN_STATE_CUM] = the factor
+ * w was multiplied by, 1 / (sigma_0 ... sigma_{n_proj - 1}).  sigma = 0 (an all-zero w or u) makes that projection the identity: w and u
+ * stay as they are, state[p] = 0, nothing is divided by zero and no NaN appears.
+ * Served shapes: Cout in {64, 128, 256, 512}, K * Cout a multiple of 256, w and u 16-byte aligned (vg_spectral_norm_blocks returns
+ * VG_EINVAL otherwise).  Item i owns the workgroups [blk0, blk0 + nblk), nblk = vg_spectral_norm_blocks(K, Cout) (VG_SN_SLAB weights
+ * each); the ranges tile [0, total_blocks) in item order.  scratch: caller-owned, vg_spectral_norm_scratch_bytes(total_blocks) bytes,
+ * 16-byte aligned; nothing is allocated and the call only enqueues.  No floating-point atomics: every sum has one fixed association,
+ * so equal inputs give bit-identical w, u and sigma on every run and on every rank.
+ * --------------------------------------------------------------------------------------------- */
+#define VG_SN_MAX_ITEMS 8
+#define VG_SN_MAX_PROJ 4
+#define VG_SN_MAX_COUT 512
+#define VG_SN_SLAB 65536
+#define VG_SN_STATE 8
+#define VG_SN_STATE_CUM 4
+typedef struct {
+    float* w; float* u; float* state;
+    int32_t K, Cout;
+    int32_t blk0, nblk;
+} vg_sn_item;
+int vg_spectral_norm_blocks(int K, int Cout);
+int64_t vg_spectral_norm_scratch_bytes(int total_blocks);
+int vg_spectral_norm(const vg_sn_item* items_dev, int T, int total_blocks, int n_proj, float* scratch, int64_t scratch_bytes,
+                     vg_stream_t stream);
 
 /* The three entry points whose per-step host scalars change from step to step -- the Philox counter, the noise standard deviation
  * (GanMonitor decays it per epoch, custom_callback.py:413-424) and Adam's bias-corrected rate lr_t -- with those scalars read from

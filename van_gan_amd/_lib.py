@@ -11,6 +11,7 @@ import torch  # noqa: F401  -- MUST precede the CDLL below: the process must use
 from . import build as _build
 
 VG_MAX_TAPS = 64
+SN_STATE, SN_STATE_CUM, SN_MAX_PROJ = 8, 4, 4     # VG_SN_STATE, VG_SN_STATE_CUM, VG_SN_MAX_PROJ
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 PAD_ZERO, PAD_REFLECT = 0, 1
 SCRATCH_CTR_BYTES = 16384          # VG_SCRATCH_CTR_BYTES
@@ -48,6 +49,10 @@ class FinDesc(C.Structure):
 class PackItem(C.Structure):
     _fields_ = [('w', c_void_p), ('tap_idx', c_void_p), ('out', c_void_p), ('Cin', c_int), ('Cout', c_int), ('ntaps', c_int),
                 ('transpose', c_int), ('CK', c_int), ('out_f32', c_int), ('blk0', c_int), ('nblk', c_int), ('bn', c_int), ('pad_', c_int)]
+
+
+class SnItem(C.Structure):
+    _fields_ = [('w', c_void_p), ('u', c_void_p), ('state', c_void_p), ('K', c_int), ('Cout', c_int), ('blk0', c_int), ('nblk', c_int)]
 
 
 class ActNormBwdDesc(C.Structure):
@@ -128,6 +133,9 @@ _SIGS = {
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),
+    'vg_spectral_norm_blocks': ([c_int, c_int], c_int),
+    'vg_spectral_norm_scratch_bytes': ([c_int], c_i64),
+    'vg_spectral_norm': ([c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p], c_int),
     'vg_local_exchange': ([c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p], c_int),
     'vg_randn_bf16': ([c_void_p, c_i64, c_float, c_u64, c_u64, c_void_p], c_int),
     'vg_dropout_mask': ([c_void_p, c_i64, c_float, c_u64, c_u64, c_void_p], c_int),
@@ -161,7 +169,7 @@ def _load(path=None, storage16=0):
         fn.restype = ret
     lib.vg_status_string.argtypes = [c_int]
     lib.vg_status_string.restype = C.c_char_p
-    for which, mirror in ((0, ConvDesc), (1, ActNormBwdDesc), (2, PackItem), (3, FinDesc)):
+    for which, mirror in ((0, ConvDesc), (1, ActNormBwdDesc), (2, PackItem), (3, FinDesc), (4, SnItem)):
         got = lib.vg_abi_sizeof(which)
         if got != C.sizeof(mirror):
             raise ImportError('libvangan_hip.so ABI mismatch: sizeof(%s) is %d in the library, %d in van_gan_amd/_lib.py '

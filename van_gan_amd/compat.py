@@ -29,8 +29,10 @@ KNOWN_GENERATORS = ('resnet', 'resUnet', 'vnet')       # vangan.py:88-124, 127-1
 
 def engine_kwargs_from_args(args, lambda_cycle=10.0, lambda_identity=5, lambda_reconstruction=5, lambda_topology=5,
                             gen_i2s='resnet', gen_s2i='resnet', semi_supervised=False, wasserstein=False,
-                            ncritic=5, gp_weight=10.0) -> Dict:
-    """Validate the reference's constructor arguments and translate them into the engine's (pure host logic)."""
+                            ncritic=5, gp_weight=10.0, use_SN=False) -> Dict:
+    """Validate the reference's constructor arguments and translate them into the engine's (pure host logic).
+    use_SN: get_discriminator's own switch (discriminator.py:16), which the reference's VanGan does not expose -- it hard-codes
+    use_SN=False at vangan.py:175,188; True maps to the engine's spectral_norm=True."""
     if gen_i2s not in KNOWN_GENERATORS:
         raise ValueError('IS Generator type not recognised')          # vangan.py:124
     if gen_s2i not in KNOWN_GENERATORS:
@@ -62,7 +64,8 @@ def engine_kwargs_from_args(args, lambda_cycle=10.0, lambda_identity=5, lambda_r
                 # wasserstein=True: what the reference trains once distributed_train_step is traced -- Wasserstein losses, the Dense head,
                 # the optimizers of vangan.py:195-203, generators every step; its gradient penalty never reaches a weight and n-critic is
                 # frozen at trace time: ncritic / gp_weight are accepted and inert
-                **(dict(wasserstein=True, lr=1e-4, beta_1=0.0, beta_2=0.9, clipnorm=0.0) if wasserstein else {}))
+                **(dict(wasserstein=True, lr=1e-4, beta_1=0.0, beta_2=0.9, clipnorm=0.0) if wasserstein else {}),
+                **(dict(spectral_norm=True) if use_SN else {}))
 
 
 def to_device_volume(t, device) -> torch.Tensor:
@@ -127,10 +130,14 @@ class ModelShim:
             return [LayerShim('conv3d')]
         # discriminator.py:50-117 in layer order: pad, input noise, conv0, IN, LeakyReLU, 3 x downsample (each with its GaussianNoise,
         # building_blocks.py:180), noise, output conv
-        out = [LayerShim('reflection_padding3d'), GaussianNoiseShim(self._eng, 'gaussian_noise'), LayerShim('conv3d'),
-               LayerShim('instance_normalization'), LayerShim('leaky_re_lu')]
+        # (use_SN: the wrapped convolutions appear as spectral_normalization layers and the InstanceNorm is gone; the noise layers stay)
+        sn = bool(getattr(self._eng, 'spectral_norm', False))
+        out = [LayerShim('reflection_padding3d'), GaussianNoiseShim(self._eng, 'gaussian_noise'),
+               LayerShim('spectral_normalization' if sn else 'conv3d')]
+        out += [LayerShim('leaky_re_lu')] if sn else [LayerShim('instance_normalization'), LayerShim('leaky_re_lu')]
         for i in range(3):
-            out += [GaussianNoiseShim(self._eng, 'gaussian_noise_%d' % (i + 1)), LayerShim('conv3d_%d' % (i + 1))]
+            out += [GaussianNoiseShim(self._eng, 'gaussian_noise_%d' % (i + 1)),
+                    LayerShim(('spectral_normalization_%d' if sn else 'conv3d_%d') % (i + 1))]
         return out + [GaussianNoiseShim(self._eng, 'gaussian_noise_4'), LayerShim('conv3d_4')]
 
     def __call__(self, x, training: bool = False):
@@ -185,10 +192,14 @@ class VanGan:
 
     def __init__(self, args, strategy=None, lambda_cycle=10.0, lambda_identity=5, lambda_reconstruction=5,
                  lambda_topology=5, gen_i2s='resnet', gen_s2i='resnet', semi_supervised=False, wasserstein=False,
-                 ncritic=5, gp_weight=10.0, *, device: str = 'cuda:0', process_group=None, seed: int = 0,
+                 ncritic=5, gp_weight=10.0, *, use_SN: bool = False, device: str = 'cuda:0', process_group=None, seed: int = 0,
                  engine_factory: Optional[Callable] = None, **engine_kw):
+        """use_SN (keyword extension behind the reference's arguments): spectrally normalised discriminators,
+        get_discriminator(use_SN=True) of discriminator.py:16,54-61,86,100.  The reference's VanGan cannot reach them -- it hard-codes
+        use_SN=False at vangan.py:175,188.  Combines with wasserstein=True."""
         kw = engine_kwargs_from_args(args, lambda_cycle, lambda_identity, lambda_reconstruction, lambda_topology, gen_i2s,
-                                     gen_s2i, semi_supervised, wasserstein, ncritic, gp_weight)
+                                     gen_s2i, semi_supervised, wasserstein, ncritic, gp_weight, use_SN)
+        self.use_SN = bool(use_SN)
         kw.update(engine_kw)
         if engine_factory is None:
             from .vangan import VanGan as engine_factory              # needs an MI355X; raises without one

@@ -1018,6 +1018,7 @@ extern "C" int vg_abi_sizeof(int which) {
         case 1: return (int)sizeof(vg_actnorm_bwd_desc);
         case 2: return (int)sizeof(vg_pack_item);
         case 3: return (int)sizeof(vg_fin_desc);
+        case 4: return (int)sizeof(vg_sn_item);
         default: return VG_EINVAL;
     }
 }

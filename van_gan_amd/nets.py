@@ -55,16 +55,29 @@ def gen_param_specs() -> List[Tuple[str, Tuple[int, ...], str]]:
     return s
 
 
-def disc_param_specs(wasserstein_patches: int = 0) -> List[Tuple[str, Tuple[int, ...], str]]:
-    """wasserstein_patches = n > 0: + the Flatten -> Dropout(0.2) -> Dense(1) head of discriminator.py:116-119 over the n patch logits."""
+SN_WRAPPED = ('conv0', 'down0', 'down1', 'down2')       # the convolutions get_discriminator(use_SN=True) wraps (discriminator.py:54-61,86,100)
+
+
+def disc_param_specs(wasserstein_patches: int = 0, spectral_norm: bool = False) -> List[Tuple[str, Tuple[int, ...], str]]:
+    """wasserstein_patches = n > 0: + the Flatten -> Dropout(0.2) -> Dense(1) head of discriminator.py:116-119 over the n patch logits.
+    spectral_norm (use_SN=True): no InstanceNorm parameters; each wrapped convolution gets the power-iteration vector `sn_u` [1, Cout]
+    of tfa.layers.SpectralNormalization (TP: non-trainable, TruncatedNormal(stddev=0.02)) -- kept by ParamStore outside the trainable
+    buffers (init 'sn_u')."""
     s: List[Tuple[str, Tuple[int, ...], str]] = []
+
+    def norm_or_u(name, co):
+        if spectral_norm:
+            s.append((name + '.sn_u', (1, co), 'sn_u'))
+        else:
+            s.append((name + '.in.gamma', (co,), 'glorot_vec')); s.append((name + '.in.beta', (co,), 'zeros'))
+
     s.append(('conv0.w', (4, 4, 4, 1, 64), 'he_normal')); s.append(('conv0.b', (64,), 'zeros'))
-    s.append(('conv0.in.gamma', (64,), 'glorot_vec')); s.append(('conv0.in.beta', (64,), 'zeros'))
+    norm_or_u('conv0', 64)
     ci = 64
     for i in range(3):
         co = ci * 2
         s.append(('down%d.w' % i, (4, 4, 4, ci, co), 'he_normal'))
-        s.append(('down%d.in.gamma' % i, (co,), 'glorot_vec')); s.append(('down%d.in.beta' % i, (co,), 'zeros'))
+        norm_or_u('down%d' % i, co)
         ci = co
     s.append(('out.w', (3, 3, 3, 512, 1), 'he_normal')); s.append(('out.b', (1,), 'zeros'))
     if wasserstein_patches:
@@ -74,24 +87,33 @@ def disc_param_specs(wasserstein_patches: int = 0) -> List[Tuple[str, Tuple[int,
 
 class ParamStore:
     """One network's parameters as flat fp32 buffers (w, grad, Adam m/v) + per-tensor views.
-    The flat gradient buffer is the RCCL all-reduce bucket of that network."""
+    The flat gradient buffer is the RCCL all-reduce bucket of that network.
+    Entries whose initialiser is 'sn_u' are non-trainable state (the spectral-normalisation vectors): they live in `state`, a flat
+    buffer of their own -- no gradient, no Adam slots, no segment of the clip / all-reduce tables -- and are loaded, exported,
+    broadcast and checkpointed with the weights."""
 
     def __init__(self, specs, device):
         self.specs = specs
         self.offsets: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
-        off = 0
+        self.state_offsets: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+        off = soff = 0
         bounds = [0]
-        for name, shape, _ in specs:
+        for name, shape, init in specs:
             n = int(math.prod(shape))
+            if init == 'sn_u':
+                self.state_offsets[name] = (soff, tuple(shape))
+                soff += n
+                continue
             self.offsets[name] = (off, tuple(shape))
             off += n
             bounds.append(off)
         self.total = off
-        self.T = len(specs)
+        self.T = len(self.offsets)
         self.w = torch.zeros(off, dtype=torch.float32, device=device)
         self.g = torch.zeros(off, dtype=torch.float32, device=device)
         self.m = torch.zeros(off, dtype=torch.float32, device=device)
         self.v = torch.zeros(off, dtype=torch.float32, device=device)
+        self.state = torch.zeros(soff, dtype=torch.float32, device=device)
         self.seg_off = torch.tensor(bounds, dtype=torch.int64, device=device)
         # T squared norms + two partial sums per 4096-element block (vg_adam_clip adds the norms in a fixed order)
         self.norms = torch.zeros(self.T + 2 * ((self.total + 4095) // 4096), dtype=torch.float32, device=device)
@@ -102,18 +124,22 @@ class ParamStore:
         return buf[off:off + int(math.prod(shape))].view(*shape)
 
     def param(self, name):
+        if name in self.state_offsets:
+            off, shape = self.state_offsets[name]
+            return self.state[off:off + int(math.prod(shape))].view(*shape)
         return self._view(self.w, name)
 
     def grad(self, name):
         return self._view(self.g, name)
 
     def load(self, tensors: Dict[str, torch.Tensor]):
-        for name, (off, shape) in self.offsets.items():
+        for name, (off, shape) in list(self.offsets.items()) + list(self.state_offsets.items()):
             self.param(name).copy_(tensors[name].to(torch.float32).reshape(shape))
 
     def export(self, buf=None) -> Dict[str, torch.Tensor]:
-        buf = self.w if buf is None else buf
-        return {name: self._view(buf, name).detach().cpu().clone() for name in self.offsets}
+        """buf None: every parameter and the non-trainable state; a buffer (gradients, Adam slots): the trainable entries."""
+        names = [n for n, _, _ in self.specs] if buf is None else list(self.offsets)
+        return {name: (self.param(name) if buf is None else self._view(buf, name)).detach().cpu().clone() for name in names}
 
 
 def init_reference(store: ParamStore, seed: int):
@@ -128,6 +154,10 @@ def init_reference(store: ParamStore, seed: int):
             t = torch.ones(shape)
         elif init == 'glorot_vec':
             t = (torch.rand(shape, generator=g) * 2 - 1) * math.sqrt(3.0 / shape[0])
+        elif init == 'sn_u':                # TP: tfa SpectralNormalization's u, TruncatedNormal(stddev=0.02) (+-2 sigma, as he_normal's)
+            t = torch.empty(shape)
+            torch.nn.init.trunc_normal_(t, 0.0, 1.0, -2.0, 2.0, generator=g)
+            t = t * 0.02
         elif init == 'glorot_dense':        # Dense kernel [in, out]
             t = (torch.rand(shape, generator=g) * 2 - 1) * math.sqrt(6.0 / (shape[0] + shape[1]))
         elif init == 'he_vec':              # he_normal over a 1-D shape (C,): Keras' _compute_fans gives fan_in = fan_out = C
@@ -830,13 +860,20 @@ class ResNetGenerator:
 # ======================================================================================================
 class PatchGAN:
     """get_discriminator (discriminator.py:7-124): reflect-pad -> noise -> Conv(64,k4,s2,bias) -> IN -> LReLU ->
-    2 x downsample(k4,s2,'valid' after reflect pad) -> downsample(k4,s1,'same') -> noise -> Conv(1,k3,'same')."""
+    2 x downsample(k4,s2,'valid' after reflect pad) -> downsample(k4,s1,'same') -> noise -> Conv(1,k3,'same').
+    spectral_norm (use_SN=True, discriminator.py:16,54-61,86,100; building_blocks.py:172-180): the four strided / 'same' convolutions
+    are wrapped in tfa.layers.SpectralNormalization and their InstanceNorm layers are gone -- SN(Conv) -> LReLU -> SpatialDropout3D.
+    The next layer's prologue then reads scale = dropout multiplier (or 1), shift = 0 per (sample, channel): LReLU(m x) = m LReLU(x)
+    for m >= 0, the folding the InstanceNorm path uses.  project() is the wrapper's power iteration (training calls only)."""
 
     NAMES = ['conv0', 'down0', 'down1', 'down2', 'out']
 
-    def __init__(self, store: ParamStore, dims: Tuple[int, int, int], dtype: torch.dtype = torch.bfloat16):
+    def __init__(self, store: ParamStore, dims: Tuple[int, int, int], dtype: torch.dtype = torch.bfloat16, spectral_norm: bool = False):
         self.dtype = dtype
         self.store, self.dims = store, tuple(dims)
+        self.spectral_norm = bool(spectral_norm)
+        if self.spectral_norm != ('conv0.sn_u' in store.state_offsets):
+            raise ValueError('PatchGAN(spectral_norm=%s) needs a store built from disc_param_specs(spectral_norm=%s)' % ((self.spectral_norm,) * 2))
         lv = [tuple(n >> i for n in dims) for i in range(4)]
         self.lv = lv
         self.ch = [1, 64, 128, 256, 512]
@@ -846,13 +883,41 @@ class PatchGAN:
         L['down1'] = ConvLayer(store, 'down1', 4, 128, 256, 2, 'reflect', False, lv[2], dtype=self.dtype)
         L['down2'] = ConvLayer(store, 'down2', 4, 256, 512, 1, 'same', False, lv[3], dtype=self.dtype)
         L['out'] = ConvLayer(store, 'out', 3, 512, 1, 1, 'same', True, lv[3], dtype=self.dtype)
-        self.Nn = {k: Norm(store, k + '.in', c) for k, c in zip(self.NAMES[:4], self.ch[1:])}
+        self.Nn = {} if self.spectral_norm else {k: Norm(store, k + '.in', c) for k, c in zip(self.NAMES[:4], self.ch[1:])}
+        self._sn = self._sn_ptab = None
+        self._sn_const = {}
         # wasserstein=True (discriminator.py:116-119): Flatten -> Dropout(0.2) -> Dense(1) over the patch logits; present when the store has it
         self.n_patch = lv[3][0] * lv[3][1] * lv[3][2]
         self.dense = 'dense.w' in store.offsets
         if self.dense:
             self.dw_, self.db_ = store.param('dense.w'), store.param('dense.b')
             self.gdw, self.gdb = store.grad('dense.w'), store.grad('dense.b')
+
+    def project(self, n: int = 2):
+        """n spectral-normalisation projections of the four wrapped kernels, back to back, in place on the fp32 master weights and the
+        stored u (vg_spectral_norm), then the repack of those four layers: the packed operands must never be older than the masters.
+        The reference applies a discriminator twice per training step (real, fake), hence n = 2 per step."""
+        if not self.spectral_norm:
+            raise RuntimeError('project() needs PatchGAN(spectral_norm=True)')
+        if self._sn is None:
+            dev = self.store.w.device
+            self._sn = ops.SpecNormTable([self.store.param(k + '.w') for k in SN_WRAPPED], [self.store.param(k + '.sn_u') for k in SN_WRAPPED], dev)
+            self._sn_ptab = ops.PackTable([self.L[k] for k in SN_WRAPPED], dev)
+        self._sn.run(n)
+        self._sn_ptab.run()
+
+    def sn_sigma(self) -> torch.Tensor:
+        """[4, n] sigma of each projection of the last project() call (device tensor; rows in SN_WRAPPED order)."""
+        return self._sn.state[:, :ops._lib.SN_MAX_PROJ]
+
+    def _sn_state(self, N: int, C_: int, mult) -> dict:
+        """The prologue arrays of the layer behind a wrapped convolution: scale = the dropout multipliers or 1, shift = 0."""
+        key = (N, C_)
+        if key not in self._sn_const:
+            dev = self.store.w.device
+            self._sn_const[key] = (torch.ones(N, C_, dtype=torch.float32, device=dev), torch.zeros(N, C_, dtype=torch.float32, device=dev))
+        one, zero = self._sn_const[key]
+        return {'scale': one if mult is None else mult, 'shift': zero, 'mult': mult}
 
     def head_forward(self, logits: torch.Tensor, mask: Optional[torch.Tensor], z: torch.Tensor):
         """z[N] = Dense(Dropout(Flatten(logits))): mask [N, n_patch] dropout multipliers (training) or None."""
@@ -884,6 +949,28 @@ class PatchGAN:
         ctx = {'N': N, 'x': x}
         src = Src(x, (N,) + lv[0], 1, f32=True, noise=noise.get('conv0'), noise_pad=1)
         acts, srcs, sts = [], [src], []
+        if self.spectral_norm:
+            # no InstanceNorm: no statistics in the epilogues, no finalisation; five convolutions
+            h = Act(ar, N, lv[1], 64, dtype=self.dtype, want_sums=False)
+            L['conv0'].forward(src, h.data)
+            acts.append(h)
+            prev_drop = None
+            for k in ['down0', 'down1', 'down2', 'out']:
+                st = self._sn_state(N, h.C, prev_drop)
+                sts.append(st)
+                lay = L[k]
+                src = Src(h.data, (N,) + tuple(lay.in_dims), h.C, scale=st['scale'], shift=st['shift'], act=ACT_LRELU,
+                          noise=noise.get(k), noise_pad=1 if lay.pad == 'reflect' else 0)
+                srcs.append(src)
+                if k == 'out':
+                    lay.forward(src, logits)
+                else:
+                    h = Act(ar, N, lay.out_dims, lay.cout, dtype=self.dtype, want_sums=False)
+                    prev_drop = drop.get(k)
+                    lay.forward(src, h.data)
+                    acts.append(h)
+            ctx.update(acts=acts, srcs=srcs, sts=sts)
+            return ctx
         tail = ops.FIN_TAIL
         h = Act(ar, N, lv[1], 64, dtype=self.dtype)
         # (ops.FIN_TAIL: the norm behind a convolution -- with that layer's channel-dropout multipliers folded in -- is finalised by the
@@ -928,9 +1015,15 @@ class PatchGAN:
             a = ctx['acts'][li - 1]
             dp = ar.alloc((N3,) + tuple(lay.buf_dims) + (lay.cin,), self.dtype)
             st = ctx['sts'][li - 1]
+            dxa = ar.alloc((N3,) + a.dims + (a.C,), self.dtype)
+            if self.spectral_norm:          # activation-only backward: dx = g * mult * LReLU'(x), nothing to reduce
+                lay.dgrad(g, N3, dp, accumulate=False)
+                ops.actnorm_bwd(dp, lay.pad == 'reflect', a.data, (N3,) + a.dims, a.C, dxa, scale=st['scale'], shift=st['shift'],
+                                mult=st['mult'], act=ACT_LRELU, norm=False, accumulate=False, alias_n0=N2, alias_shift=B)
+                g = dxa
+                continue
             nrm = Nn[self.NAMES[li - 1]]
             red = ops.alloc_red(ar, N3, a.C)
-            dxa = ar.alloc((N3,) + a.dims + (a.C,), self.dtype)
             dsc = ops.actnorm_desc(dp, lay.pad == 'reflect', a.data, (N3,) + a.dims, a.C, dxa, scale=st['scale'], shift=st['shift'],
                                    mult=st['mult'], act=ACT_LRELU, norm=True, gamma=nrm.gamma, mean=st['mean'], rstd=st['rstd'], red=red,
                                    accumulate=False, dgamma=nrm.dgamma, dbeta=nrm.dbeta, alias_n0=N2, alias_shift=B, pgrad_n=N2)
@@ -969,9 +1062,14 @@ class PatchGAN:
             dp = ar.alloc((N,) + tuple(lay.buf_dims) + (lay.cin,), self.dtype)
             lay.dgrad(g, N, dp, accumulate=False)
             st = ctx['sts'][li - 1]
+            dxa = ar.alloc((N,) + a.dims + (a.C,), self.dtype)
+            if self.spectral_norm:
+                ops.actnorm_bwd(dp, lay.pad == 'reflect', sl(a.data), (N,) + a.dims, a.C, dxa, scale=sl(st['scale']), shift=sl(st['shift']),
+                                mult=sl(st['mult']), act=ACT_LRELU, norm=False, accumulate=False)
+                g = dxa
+                continue
             nrm = Nn[self.NAMES[li - 1]]
             red = ops.alloc_red(ar, N, a.C)
-            dxa = ar.alloc((N,) + a.dims + (a.C,), self.dtype)
             ops.actnorm_bwd(dp, lay.pad == 'reflect', sl(a.data), (N,) + a.dims, a.C, dxa, scale=sl(st['scale']),
                             shift=sl(st['shift']), mult=sl(st['mult']), act=ACT_LRELU, norm=True, gamma=nrm.gamma,
                             mean=sl(st['mean']), rstd=sl(st['rstd']), red=red, accumulate=False,

@@ -1270,6 +1270,38 @@ class PackTable:
             l.pack_up()
 
 
+class SpecNormTable:
+    """The wrapped kernels of one network for vg_spectral_norm: device item table, caller-owned scratch and the fp32 state block
+    ([i][p] = sigma of projection p of the last call, [i][SN_STATE_CUM] = the factor the kernel was multiplied by).
+    ws / us: fp32 tensors, ws[i] a Keras-layout kernel [..., Cout] (a view of the master weights: projected IN PLACE), us[i] its
+    power-iteration vector ([1, Cout], overwritten)."""
+
+    def __init__(self, ws, us, device):
+        assert 0 < len(ws) == len(us) <= 8
+        arr = (_lib.SnItem * len(ws))()
+        self.state = torch.zeros(len(ws), _lib.SN_STATE, dtype=torch.float32, device=device)
+        blk = 0
+        for i, (a, w, u) in enumerate(zip(arr, ws, us)):
+            cout = w.shape[-1]
+            K = w.numel() // cout
+            nblk = _lib.lib.vg_spectral_norm_blocks(K, cout)
+            if (nblk < 1 or w.dtype != torch.float32 or u.dtype != torch.float32 or u.numel() != cout or not w.is_contiguous()
+                    or not u.is_contiguous() or (w.data_ptr() | u.data_ptr()) & 15):
+                raise ValueError('vg_spectral_norm does not serve a [%d, %d] kernel (Cout in 64/128/256/512, K * Cout a multiple of 256, '
+                                 'contiguous 16-byte aligned fp32)' % (K, cout))
+            a.w, a.u, a.state = w.data_ptr(), u.data_ptr(), self.state[i].data_ptr()
+            a.K, a.Cout, a.blk0, a.nblk = K, cout, blk, nblk
+            blk += nblk
+        self.total_blocks, self.n = blk, len(ws)
+        self.keep = (list(ws), list(us))
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+        self.scratch = torch.empty(_lib.lib.vg_spectral_norm_scratch_bytes(blk) // 4, dtype=torch.float32, device=device)
+
+    def run(self, n_proj: int = 1):
+        check(lib.vg_spectral_norm(_p(self.table), self.n, self.total_blocks, n_proj, _p(self.scratch), self.scratch.numel() * 4, stream()),
+              'vg_spectral_norm')
+
+
 # ------------------------------------------------------------------------------------------------------
 # InstanceNorm helpers
 # ------------------------------------------------------------------------------------------------------

@@ -113,8 +113,12 @@ class VanGan:
                  beta_1: float = 0.5, beta_2: float = 0.9, clipnorm: float = 100.0, layer_noise: float = 0.1,
                  dropout_rate: float = 0.2, skel_iters: int = 15, output_dir: Optional[str] = None,
                  process_group=None, arena_bytes: Optional[int] = None, precision: str = 'bf16', generator: str = 'resUnet',
-                 wasserstein: bool = False):
-        """wasserstein=True: what the reference's wasserstein=True trains once its step is traced: Wasserstein critic /
+                 wasserstein: bool = False, spectral_norm: bool = False):
+        """spectral_norm=True: the discriminators of get_discriminator(use_SN=True) (discriminator.py:16,54-61,86,100): the four wrapped
+        convolutions are spectrally normalised, no InstanceNorm.  Every train step projects each wrapped kernel twice (the reference
+        applies a discriminator to the real and to the fake batch: two training calls of the wrapper) before the discriminator's
+        [real; fake] application; test_step / generate never project.  Combines with wasserstein=True.  DESIGN.md section 8.
+        wasserstein=True: what the reference's wasserstein=True trains once its step is traced: Wasserstein critic /
         generator losses (loss_functions.py:325-355), discriminators with the Flatten -> Dropout(0.2) -> Dense(1) head
         (discriminator.py:116-119), generators updated every step, no gradient penalty (the reference's never reaches a weight).  Pass the
         optimizers of vangan.py:195-203 explicitly: lr=1e-4, beta_1=0.0, beta_2=0.9, clipnorm=0 (compat.VanGan does)."""
@@ -126,6 +130,7 @@ class VanGan:
             raise ValueError("generator must be 'resUnet' (default, vangan.py:113-123) or 'resnet' (vangan.py:88-97)")
         self.generator = generator                # both generators of one engine have the same architecture
         self.wasserstein = bool(wasserstein)
+        self.spectral_norm = bool(spectral_norm)
         self.precision = precision
         self.dtype = torch.bfloat16 if precision == 'bf16' else torch.float32
         self.device = torch.device(device)
@@ -163,14 +168,14 @@ class VanGan:
         for i, name in enumerate(NETS):
             gspecs = gen_param_specs() if generator == 'resUnet' else resnet_param_specs()
             n_patch = (self.dims[0] // 8) * (self.dims[1] // 8) * (self.dims[2] // 8) if self.wasserstein else 0
-            st = ParamStore(gspecs if name.startswith('gen') else disc_param_specs(n_patch), self.device)
+            st = ParamStore(gspecs if name.startswith('gen') else disc_param_specs(n_patch, self.spectral_norm), self.device)
             init_reference(st, seed + i)
             self.stores[name] = st
         GenNet = ResUNet if generator == 'resUnet' else ResNetGenerator
         self.gen_IS = GenNet(self.stores['gen_IS'], self.dims, self.dtype)
         self.gen_SI = GenNet(self.stores['gen_SI'], self.dims, self.dtype)
-        self.disc_I = PatchGAN(self.stores['disc_I'], self.dims, self.dtype)
-        self.disc_S = PatchGAN(self.stores['disc_S'], self.dims, self.dtype)
+        self.disc_I = PatchGAN(self.stores['disc_I'], self.dims, self.dtype, spectral_norm=self.spectral_norm)
+        self.disc_S = PatchGAN(self.stores['disc_S'], self.dims, self.dtype, spectral_norm=self.spectral_norm)
         self.nets = {'gen_IS': self.gen_IS, 'gen_SI': self.gen_SI, 'disc_I': self.disc_I, 'disc_S': self.disc_S}
         S = self.dims[0] * self.dims[1] * self.dims[2]
         if arena_bytes is None:
@@ -214,7 +219,9 @@ class VanGan:
         # one arena for every backward sweep (VG_LANES=0): the workspace is sized for the two-lane layout, so backward temporaries
         # are recycled there (joining release) instead of being kept until the next reset
         self.arena.lazy_ok = self._lane_b is not None
-        self.sync = GradSync({k: s.g for k, s in self.stores.items()}, self.pg, {k: s.w for k, s in self.stores.items()}, stream=comm)
+        bcast = {k: s.w for k, s in self.stores.items()}
+        bcast.update({k + '.sn_u': s.state for k, s in self.stores.items() if s.state.numel()})      # rank 0's u as well: replicas never exchange it again
+        self.sync = GradSync({k: s.g for k, s in self.stores.items()}, self.pg, bcast, stream=comm)
         self.ddp = self.sync.active
         self._inline = _INLINE if (_INLINE_ENV is not None or not self.ddp) else 1      # (see _INLINE)
         self._tl = [] if os.environ.get('VG_TIMELINE') == '1' else None
@@ -516,6 +523,11 @@ class VanGan:
             noise, drop = noise or {}, drop or {}
             nzS, dpS, nzI, dpI = noise.get('S'), drop.get('S'), noise.get('I'), drop.get('I')
         self._need('disc_S', 'disc_I')
+        if self.spectral_norm and training:
+            # TP: tfa SpectralNormalization projects once per training call, the reference calls a discriminator on the real and on the
+            # fake batch -- two projections per step, back to back, then the repack; the batched [real; fake] application runs on the result
+            self.disc_S.project(2)
+            self.disc_I.project(2)
         dS = self.disc_S.forward(ar, bufS, logS, nzS, dpS)                                  # lane A: needs fake_S
         gd = 1.0 / (nps * gbs)
         # upstream gradients at the patch logits, adjacent: [d critic loss (2B: real, fake); d generator loss (B: fake)] -- one 3B-sample
@@ -859,6 +871,8 @@ class VanGan:
         are those of the engine at capture time.  The library has been capture-legal since it stopped allocating (vg_conv_desc::scratch)."""
         if self.sync.active:
             raise NotImplementedError('graph capture covers the single-process step (the gradient all-reduce is not captured)')
+        if self.spectral_norm:
+            raise NotImplementedError('graph capture is not built for spectral_norm=True: use train_step')
         ops.set_device(self.device.index)
         B, (D, H, W) = self.batch_size, self.dims
         self._g_in = (torch.zeros(B, D, H, W, 1, device=self.device), torch.zeros(B, D, H, W, 1, device=self.device))
@@ -910,6 +924,8 @@ class VanGan:
 
     def train_step_graph(self, real_I: torch.Tensor, real_S: torch.Tensor, sync: bool = True):
         """One train step by replaying the captured graph (capture_train_step): same arithmetic, same streams' dependencies."""
+        if self.spectral_norm:
+            raise NotImplementedError('graph capture is not built for spectral_norm=True: use train_step')
         if self._graph is None:
             self.capture_train_step()
         ops.set_device(self.device.index)
@@ -931,6 +947,8 @@ class VanGan:
         weights and the noise on/off decision are those of the first call."""
         if self.sync.active:
             raise NotImplementedError('the launch list covers the single-process step (no all-reduce)')
+        if self.spectral_norm:
+            raise NotImplementedError('the launch list is not built for spectral_norm=True: use train_step')
         ops.set_device(self.device.index)
         if getattr(self, '_rlist', None) is None:
             B, (D, H, W) = self.batch_size, self.dims
@@ -1037,6 +1055,9 @@ class VanGan:
         if self.rank == 0:
             torch.cuda.synchronize(self.device)
             blob = {k: dict(w=s.w.cpu(), m=s.m.cpu(), v=s.v.cpu(), step=s.step) for k, s in self.stores.items()}
+            for k, s in self.stores.items():
+                if s.state.numel():
+                    blob[k]['sn_u'] = s.state.cpu()
             blob['_rng_offset'] = int(self.rng_offset)
             tmp = path + '.tmp.%d' % os.getpid()
             torch.save(blob, tmp)
@@ -1054,9 +1075,17 @@ class VanGan:
             print('Error: Checkpoint not found!')                  # vangan.py:267-268: prints, does not raise
             return False
         ck = torch.load(path, map_location='cpu')
+        for k, s in self.stores.items():         # nothing is loaded from a checkpoint of another configuration
+            has = 'sn_u' in ck[k]
+            if has != bool(s.state.numel()) or ck[k]['w'].numel() != s.w.numel() or (has and ck[k]['sn_u'].numel() != s.state.numel()):
+                raise ValueError('%s: %s was written %s spectral normalisation (%d weights), this engine is built %s it (%d weights)'
+                                 % (path, k, 'with' if has else 'without', ck[k]['w'].numel(),
+                                    'with' if s.state.numel() else 'without', s.w.numel()))
         self._join_updates()            # (see load_weights): the optimizer stream may still hold the last step's Adam + repack
         for k, s in self.stores.items():
             s.w.copy_(ck[k]['w']); s.m.copy_(ck[k]['m']); s.v.copy_(ck[k]['v']); s.step = ck[k]['step']
+            if s.state.numel():
+                s.state.copy_(ck[k]['sn_u'])
         self.rng_offset = int(ck.get('_rng_offset', 0))
         self.repack()
         return True
