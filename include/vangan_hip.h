@@ -497,6 +497,28 @@ int64_t vg_spectral_norm_scratch_bytes(int total_blocks);
 int vg_spectral_norm(const vg_sn_item* items_dev, int T, int total_blocks, int n_proj, float* scratch, int64_t scratch_bytes,
                      vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Attention gate of the ResUNet decoder (ResUNet(use_attention_gate=True), resunet_model.py:178-179 / vnet_model.py:24-77), restated:
+ *   q = relu(skip . w_theta + b_theta + phi[parent]);  h = sigmoid(q . w_psi + b_psi);  gated = skip * h.
+ * skip / gated / dg / dskip [N][D][H][W][Cs], phi / dphi [N][D/2][H/2][W/2][Ci] (the 1x1x1 convolution of the low-resolution tensor, its
+ * bias included: it commutes with UpSampling3D(2) and is read through the parent index), all in the build's 16-bit format or, f32 != 0,
+ * float32 (exact-parity mode); h [N][D][H][W] float32; w_theta [Cs][Ci], b_theta [Ci], w_psi [Ci], b_psi [1] are the fp32 master
+ * parameters in Keras layout (rounded to the storage format on the matrix pipe; 4-byte alignment suffices).
+ * Served shapes: D, H, W even, (Cs, Ci) in {(16, 32), (32, 64), (64, 128), (128, 256)}; tensors 16-byte aligned; else VG_EINVAL.
+ * vg_attn_gate_fwd also ADDS the per-(n, c) (sum, sum of squares) of the STORED gated values into sums [VG_STRIPES][N][Cs][2].
+ * vg_attn_gate_bwd recomputes q, writes dskip = dg * h + dq . w_theta^T (accumulate != 0: adds to what dskip holds), dphi = the sum of
+ * dq over the 8 children of each low-resolution voxel, and ADDS dw_theta, db_theta, dw_psi, db_psi (reduced per workgroup on chip, then
+ * one float atomic per workgroup and destination: the sums' last bits may differ from run to run).
+ * Neither call allocates or synchronises.
+ * --------------------------------------------------------------------------------------------- */
+int vg_attn_gate_fwd(const void* skip, const void* phi, const float* w_theta, const float* b_theta, const float* w_psi,
+                     const float* b_psi, int N, int D, int H, int W, int Cs, int Ci, int f32, void* gated, float* h, float* sums,
+                     vg_stream_t stream);
+int vg_attn_gate_bwd(const void* dg, const void* skip, const float* h, const void* phi, const float* w_theta,
+                     const float* b_theta, const float* w_psi, int N, int D, int H, int W, int Cs, int Ci, int f32, void* dskip,
+                     int accumulate, void* dphi, float* dw_theta, float* db_theta, float* dw_psi, float* db_psi,
+                     vg_stream_t stream);
+
 /* The three entry points whose per-step host scalars change from step to step -- the Philox counter, the noise standard deviation
  * (GanMonitor decays it per epoch, custom_callback.py:413-424) and Adam's bias-corrected rate lr_t -- with those scalars read from
  * DEVICE memory: a HIP graph captured over one VanGan.train_step (vangan.py:380-440) is then replayable, the host refreshing a

@@ -136,6 +136,8 @@ _SIGS = {
     'vg_spectral_norm_blocks': ([c_int, c_int], c_int),
     'vg_spectral_norm_scratch_bytes': ([c_int], c_i64),
     'vg_spectral_norm': ([c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p], c_int),
+    'vg_attn_gate_fwd': ([c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4, c_int),
+    'vg_attn_gate_bwd': ([c_void_p] * 7 + [c_int] * 7 + [c_void_p, c_int] + [c_void_p] * 6, c_int),
     'vg_local_exchange': ([c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p], c_int),
     'vg_randn_bf16': ([c_void_p, c_i64, c_float, c_u64, c_u64, c_void_p], c_int),
     'vg_dropout_mask': ([c_void_p, c_i64, c_float, c_u64, c_u64, c_void_p], c_int),

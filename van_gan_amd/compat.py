@@ -29,10 +29,12 @@ KNOWN_GENERATORS = ('resnet', 'resUnet', 'vnet')       # vangan.py:88-124, 127-1
 
 def engine_kwargs_from_args(args, lambda_cycle=10.0, lambda_identity=5, lambda_reconstruction=5, lambda_topology=5,
                             gen_i2s='resnet', gen_s2i='resnet', semi_supervised=False, wasserstein=False,
-                            ncritic=5, gp_weight=10.0, use_SN=False) -> Dict:
+                            ncritic=5, gp_weight=10.0, use_SN=False, use_attention_gate=False) -> Dict:
     """Validate the reference's constructor arguments and translate them into the engine's (pure host logic).
     use_SN: get_discriminator's own switch (discriminator.py:16), which the reference's VanGan does not expose -- it hard-codes
-    use_SN=False at vangan.py:175,188; True maps to the engine's spectral_norm=True."""
+    use_SN=False at vangan.py:175,188; True maps to the engine's spectral_norm=True.
+    use_attention_gate: ResUNet's own switch (resunet_model.py:152), hard-coded to False at vangan.py:118,157; True maps to the engine's
+    attention_gate=True and needs the 'resUnet' generators."""
     if gen_i2s not in KNOWN_GENERATORS:
         raise ValueError('IS Generator type not recognised')          # vangan.py:124
     if gen_s2i not in KNOWN_GENERATORS:
@@ -41,6 +43,8 @@ def engine_kwargs_from_args(args, lambda_cycle=10.0, lambda_identity=5, lambda_r
         raise NotImplementedError("train_step is built for gen_i2s == gen_s2i == 'resUnet' (the default, main.py:196-200) and, SURVEY "
                                   "section 8(f)4, for gen_i2s == gen_s2i == 'resnet' (generator.py:7-73: van_gan_amd.nets.ResNetGenerator, "
                                   "tests/test_gpu_resnet.py); 'vnet' and mixed pairs are not built")
+    if use_attention_gate and gen_i2s != 'resUnet':
+        raise ValueError("use_attention_gate=True is an option of the 'resUnet' generator (resunet_model.py:152), not of '%s'" % gen_i2s)
     if semi_supervised:
         raise NotImplementedError('semi_supervised is never enabled by main.py and is not built')
     if int(args.DIMENSIONS) != 3:
@@ -65,7 +69,8 @@ def engine_kwargs_from_args(args, lambda_cycle=10.0, lambda_identity=5, lambda_r
                 # the optimizers of vangan.py:195-203, generators every step; its gradient penalty never reaches a weight and n-critic is
                 # frozen at trace time: ncritic / gp_weight are accepted and inert
                 **(dict(wasserstein=True, lr=1e-4, beta_1=0.0, beta_2=0.9, clipnorm=0.0) if wasserstein else {}),
-                **(dict(spectral_norm=True) if use_SN else {}))
+                **(dict(spectral_norm=True) if use_SN else {}),
+                **(dict(attention_gate=True) if use_attention_gate else {}))
 
 
 def to_device_volume(t, device) -> torch.Tensor:
@@ -192,14 +197,17 @@ class VanGan:
 
     def __init__(self, args, strategy=None, lambda_cycle=10.0, lambda_identity=5, lambda_reconstruction=5,
                  lambda_topology=5, gen_i2s='resnet', gen_s2i='resnet', semi_supervised=False, wasserstein=False,
-                 ncritic=5, gp_weight=10.0, *, use_SN: bool = False, device: str = 'cuda:0', process_group=None, seed: int = 0,
+                 ncritic=5, gp_weight=10.0, *, use_SN: bool = False, use_attention_gate: bool = False, device: str = 'cuda:0', process_group=None, seed: int = 0,
                  engine_factory: Optional[Callable] = None, **engine_kw):
         """use_SN (keyword extension behind the reference's arguments): spectrally normalised discriminators,
         get_discriminator(use_SN=True) of discriminator.py:16,54-61,86,100.  The reference's VanGan cannot reach them -- it hard-codes
-        use_SN=False at vangan.py:175,188.  Combines with wasserstein=True."""
+        use_SN=False at vangan.py:175,188.  Combines with wasserstein=True.
+        use_attention_gate (the same kind of extension): both generators are ResUNet(use_attention_gate=True) (resunet_model.py:152,
+        178-179), which the reference's VanGan hard-codes to False at vangan.py:118,157; needs gen_i2s == gen_s2i == 'resUnet'."""
         kw = engine_kwargs_from_args(args, lambda_cycle, lambda_identity, lambda_reconstruction, lambda_topology, gen_i2s,
-                                     gen_s2i, semi_supervised, wasserstein, ncritic, gp_weight, use_SN)
+                                     gen_s2i, semi_supervised, wasserstein, ncritic, gp_weight, use_SN, use_attention_gate)
         self.use_SN = bool(use_SN)
+        self.use_attention_gate = bool(use_attention_gate)
         kw.update(engine_kw)
         if engine_factory is None:
             from .vangan import VanGan as engine_factory              # needs an MI355X; raises without one

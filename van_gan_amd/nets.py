@@ -26,7 +26,10 @@ _STEM_AUX = os.environ.get('VG_STEM_AUX', '1') != '0'      # the stem shortcut's
 _STEM_FUSED = os.environ.get('VG_STEM_FUSED', '1') != '0'
 
 
-def gen_param_specs() -> List[Tuple[str, Tuple[int, ...], str]]:
+def gen_param_specs(attention_gate: bool = False) -> List[Tuple[str, Tuple[int, ...], str]]:
+    """attention_gate (ResUNet(use_attention_gate=True), resunet_model.py:178-179): per decoder level the three 1x1x1 convolutions of
+    attention_gate (vnet_model.py:24-77) -- theta on the skip tensor, phi on the upsampled tensor, psi to one channel -- in creation
+    order, in front of the level's residual block: 132 004 parameters in 24 tensors."""
     f = GEN_F
     s: List[Tuple[str, Tuple[int, ...], str]] = []
 
@@ -50,6 +53,10 @@ def gen_param_specs() -> List[Tuple[str, Tuple[int, ...], str]]:
     inorm('bridge.cb1.in', f[4]); conv('bridge.cb1.conv', 3, f[4], f[4], 'he_normal')
     inorm('bridge.cb2.in', f[4]); conv('bridge.cb2.conv', 3, f[4], f[4], 'he_normal')
     for d in (3, 2, 1, 0):
+        if attention_gate:
+            conv('dec%d.gate.theta' % d, 1, f[d], f[d + 1], 'he_normal')
+            conv('dec%d.gate.phi' % d, 1, f[d + 1], f[d + 1], 'he_normal')
+            conv('dec%d.gate.psi' % d, 1, f[d + 1], 1, 'he_normal')
         resblock('dec%d' % d, f[d + 1] + f[d], f[d])
     conv('out', 1, f[0], 1, 'glorot_uniform')
     return s
@@ -297,7 +304,9 @@ def pair_ctx(ar: Arena, ctx: dict, x_full: torch.Tensor, ys, lv0) -> dict:
 # ======================================================================================================
 class ResUNet:
     def __init__(self, store: ParamStore, dims: Tuple[int, int, int], dtype: torch.dtype = torch.bfloat16,
-                 upsample_mode: str = 'simple'):
+                 upsample_mode: str = 'simple', attention_gate: bool = False):
+        # attention_gate: every decoder level multiplies its skip tensor by a learned per-voxel gate before the concatenation
+        # (gen_param_specs(True); vg_attngate.hip).  The store must have been built from the gated specs.
         # resunet_model.py:185-249 as vangan.py:112-122,151-162 configures it: upsample_mode='simple' (UpSampling3D).  The
         # reference's other mode cannot be built by the reference itself: 'deconv' reflect-pads before its k2 s2
         # Conv3DTranspose (resunet_model.py:168-174, padding='valid' is never overridden at :241), which yields 2(S+2) voxels
@@ -309,6 +318,10 @@ class ResUNet:
         if upsample_mode != 'simple':
             raise ValueError("upsample_mode must be 'simple' (UpSampling3D(2), vangan.py:114,153)")
         self.dtype = dtype
+        self.attention_gate = bool(attention_gate)
+        if self.attention_gate != ('dec0.gate.theta.w' in store.offsets):
+            raise ValueError('ResUNet(attention_gate=%s) needs a parameter store built from gen_param_specs(%s)'
+                             % (self.attention_gate, self.attention_gate))
         D, H, W = dims
         if any(n % 16 or n < 32 for n in dims):
             raise ValueError('spatial dims must be multiples of 16 and >= 32 (4 stride-2 stages + reflect pad)')
@@ -339,6 +352,10 @@ class ResUNet:
         for d in (3, 2, 1, 0):
             resblock('dec%d' % d, f[d + 1] + f[d], f[d], 1, lv[d], lv[d])
             L['dec%d.cb1' % d].enable_up(f[d + 1])            # its first f[d+1] input channels are the upsampled low-resolution tensor
+            if self.attention_gate:
+                # phi reads the UPSAMPLED tensor in the reference; a 1x1x1 convolution commutes with nearest-neighbour upsampling, so it
+                # runs on the low grid (an eighth of the work) and the gate kernel reads it through the parent index
+                L['dec%d.gate.phi' % d] = ConvLayer(store, 'dec%d.gate.phi' % d, 1, f[d + 1], f[d + 1], 1, 'same', True, lv[d + 1], dtype=self.dtype)
         L['out'] = ConvLayer(store, 'out', 1, f[0], 1, 1, 'same', True, lv[0], dtype=self.dtype)
 
     def pack(self):
@@ -347,17 +364,55 @@ class ResUNet:
         self._ptab.run()
 
     # ---------------------------------------------------------------------------------------------
+    def _gate_params(self, d: int, grad: bool = False):
+        get = self.store.grad if grad else self.store.param
+        return tuple(get('dec%d.gate.%s' % (d, k)) for k in ('theta.w', 'theta.b', 'psi.w', 'psi.b'))
+
+    def _gate_fwd(self, ar: Arena, d: int, N: int, low: Act, skip: Act):
+        """attention_gate + attention_concat's multiply (vnet_model.py:24-77) of decoder level d: returns the gated skip tensor (an Act
+        whose sums the gate launch fills: the level's first InstanceNorm takes its skip-half statistics from it) and what the backward
+        needs.  phi is a storage point (the engine's storage type), h is kept as fp32 [N, D, H, W]; theta and q are never stored."""
+        f, lv = GEN_F, self.lv
+        phi = Act(ar, N, lv[d + 1], f[d + 1], dtype=self.dtype, want_sums=False)
+        sphi = Src(low.data, (N,) + lv[d + 1], f[d + 1])
+        self.L['dec%d.gate.phi' % d].forward(sphi, phi.data)
+        gs = Act(ar, N, lv[d], f[d], dtype=self.dtype)
+        hmap = ar.alloc((N,) + lv[d], torch.float32)
+        wt, bt, wp, bp = self._gate_params(d)
+        ops.attn_gate_fwd(skip.data, phi.data, wt, bt, wp, bp, (N,) + lv[d], f[d], f[d + 1], gs.data, hmap, gs.sums)
+        return gs, dict(skip=skip, phi=phi, sphi=sphi, h=hmap)
+
+    def _gate_bwd(self, ar: Arena, d: int, c: dict, N: int):
+        """Backward of _gate_fwd once the decoder block has written the gradient of its skip half into the gated tensor's buffer: the
+        encoder activation's gradient (first writer of that buffer), d_phi on the low grid, the gate's parameter gradients; then phi's
+        own weight gradient and its data gradient into the low-resolution tensor's buffer (behind the concat backward's first write)."""
+        low, gs = c['inp']
+        gc = c['gate']
+        skip, phi = gc['skip'], gc['phi']
+        lay = self.L['dec%d.gate.phi' % d]
+        assert low.grad_init, 'the concat backward must have written the low-resolution gradient first'
+        mk = ar.mark()
+        dphi = ar.alloc(phi.data.shape, self.dtype)
+        wt, bt, wp, _ = self._gate_params(d)
+        gwt, gbt, gwp, gbp = self._gate_params(d, grad=True)
+        ops.attn_gate_bwd(gs.grad, skip.data, gc['h'], phi.data, wt, bt, wp, (N,) + skip.dims, skip.C, phi.C, skip.grad,
+                          not skip.first_write(), dphi, gwt, gbt, gwp, gbp)
+        lay.wgrad(gc['sphi'], dphi)
+        lay.dgrad(dphi, N, low.grad, accumulate=True)
+        ar.release(mk, defer=True)
+
     def _block_fwd(self, ar: Arena, name: str, N: int, src_raw: Src, nrm_inputs, out_dims, co, ctx, save: bool = True, n1=None,
-                   out_jobs=None):
+                   out_jobs=None, out: Optional[Act] = None):
         """residual_block (resunet_model.py:103-143): out = conv2(relu(IN(conv1(relu(IN(x)))))) + IN(short(x)).
         save=False (inference): the block output is allocated first and everything else the block allocates (r, the
         shortcut, the InstanceNorm scale/shift vectors) is handed back to the arena once the block's kernels are queued.
         n1 / out_jobs (ops.FIN_TAIL): the state of the block's first norm, already filled by the launches that produced its input, and
         the consumer entries (Norm.job) of the norms that read the block's OUTPUT -- finalised by the block's last convolution."""
         L, Nn = self.L, self.Nn
-        out = mk = None
+        mk = None
         if not save:
-            out = Act(ar, N, out_dims, co, dtype=self.dtype)
+            if out is None:
+                out = Act(ar, N, out_dims, co, dtype=self.dtype)
             mk = ar.mark()
         tail = n1 is not None
         if not tail:
@@ -411,22 +466,26 @@ class ResUNet:
         # FIRST norm reads the previous block's output (a decoder block's: [upsampled low-resolution output; encoder skip], two
         # producers, two channel ranges of one array), so those states exist before the first launch.
         tail = ops.FIN_TAIL
+        gate = self.attention_gate
         pre, jobs = {}, {}
         if tail:
             pre['stem.cb'], pre['stem.short'] = Nn['stem.cb'].state(ar, N), Nn['stem.short'].state(ar, N)
-            for b in ['enc%d' % e for e in range(1, 5)] + ['dec%d' % d for d in (3, 2, 1, 0)]:
+            # (attention gate: a decoder block's first norm reads [upsampled low output; GATED skip]; its state is finalised by one
+            #  vg_in_finalize launch behind the gate, from low.sums and the gate launch's sums -- no state here, no producer entry below)
+            for b in ['enc%d' % e for e in range(1, 5)] + ([] if gate else ['dec%d' % d for d in (3, 2, 1, 0)]):
                 pre[b] = Nn[b + '.cb1'].state(ar, N)
             pre['bridge.cb1'], pre['bridge.cb2'] = Nn['bridge.cb1'].state(ar, N), Nn['bridge.cb2'].state(ar, N)
             # consumers of every block output: skips[d] (stem, enc1..enc3) feeds enc(d+1).cb1 and, behind the f[d+1] upsampled
             # channels, dec(d).cb1; enc4 feeds the bridge; bridge / dec outputs feed the next decoder block's low half
-            jobs['stem'] = [Nn['enc1.cb1'].job(pre['enc1']), Nn['dec0.cb1'].job(pre['dec0'], f[1])]
+            dec_job = (lambda d, c_off=0: []) if gate else (lambda d, c_off=0: [Nn['dec%d.cb1' % d].job(pre['dec%d' % d], c_off)])
+            jobs['stem'] = [Nn['enc1.cb1'].job(pre['enc1'])] + dec_job(0, f[1])
             for e in range(1, 4):
-                jobs['enc%d' % e] = [Nn['enc%d.cb1' % (e + 1)].job(pre['enc%d' % (e + 1)]), Nn['dec%d.cb1' % e].job(pre['dec%d' % e], f[e + 1])]
+                jobs['enc%d' % e] = [Nn['enc%d.cb1' % (e + 1)].job(pre['enc%d' % (e + 1)])] + dec_job(e, f[e + 1])
             jobs['enc4'] = [Nn['bridge.cb1'].job(pre['bridge.cb1'])]
             jobs['bridge.cb1'] = [Nn['bridge.cb2'].job(pre['bridge.cb2'])]
-            jobs['bridge.cb2'] = [Nn['dec3.cb1'].job(pre['dec3'])]
+            jobs['bridge.cb2'] = dec_job(3)
             for d in (3, 2, 1):
-                jobs['dec%d' % d] = [Nn['dec%d.cb1' % (d - 1)].job(pre['dec%d' % (d - 1)])]
+                jobs['dec%d' % d] = dec_job(d - 1)
             jobs['dec0'] = None
         sx = Src(x, (N,) + lv[0], 1, f32=True)
         c1 = Act(ar, N, lv[0], f[0], dtype=self.dtype)
@@ -464,7 +523,7 @@ class ResUNet:
         nb2 = pre['bridge.cb2'] if tail else Nn['bridge.cb2'].finalize(ar, b1)
         sb2 = Src(b1.data, (N,) + lv[4], f[4], scale=nb2['scale'], shift=nb2['shift'], act=ACT_RELU)
         b2 = Act(ar, N, lv[4], f[4], dtype=self.dtype)
-        L['bridge.cb2'].forward(sb2, b2.data, sums=b2.sums, fin=ops.fin_desc(ar, b2.count, jobs['bridge.cb2']) if tail else None)
+        L['bridge.cb2'].forward(sb2, b2.data, sums=b2.sums, fin=ops.fin_desc(ar, b2.count, jobs['bridge.cb2']) if (tail and jobs['bridge.cb2']) else None)
         ctx['bridge'] = dict(inp=h, nb1=nb1, sb1=sb1, b1=b1, nb2=nb2, sb2=sb2, b2=b2)
         h = b2
         for d in (3, 2, 1, 0):
@@ -473,6 +532,21 @@ class ResUNet:
             low = h
             yield
             b = 'dec%d' % d
+            if self.attention_gate:
+                out_pre = mkg = None
+                if not save:                     # inference: the block output first, the gate's temporaries are recycled with the block's
+                    out_pre = Act(ar, N, lv[d], f[d], dtype=self.dtype)
+                    mkg = ar.mark()
+                gs, gctx = self._gate_fwd(ar, d, N, low, skip)
+                raw = Src(low.data, (N,) + lv[d], low.C, gs.data, gs.C, shift0=1)
+                n1 = Nn[b + '.cb1'].finalize(ar, low, gs) if tail else None
+                h = self._block_fwd(ar, b, N, raw, (low, gs), lv[d], f[d], ctx, save, n1=n1, out_jobs=jobs.get(b), out=out_pre)
+                if save:
+                    ctx[b]['inp'] = (low, gs)
+                    ctx[b]['gate'] = gctx
+                else:
+                    ar.release(mkg)
+                continue
             h = self._block_fwd(ar, b, N, raw, (low, skip), lv[d], f[d], ctx, save, n1=pre.get(b), out_jobs=jobs.get(b))
             if save:
                 ctx['dec%d' % d]['inp'] = (low, skip)
@@ -570,6 +644,8 @@ class ResUNet:
         # gradient buffers of every tensor that has more than one consumer / is read across blocks
         acts = [ctx['stem']['out']] + [ctx['enc%d' % e]['out'] for e in range(1, 5)] + \
                [ctx['bridge']['b2']] + [ctx['dec%d' % d]['out'] for d in (3, 2, 1, 0)]
+        if self.attention_gate:                 # the gated skip tensors: the decoder blocks write their skip-half gradient there
+            acts += [ctx['dec%d' % d]['inp'][1] for d in (3, 2, 1, 0)]
         for a in acts:
             a.grad = None
             a.alloc_grad(ar)
@@ -586,6 +662,8 @@ class ResUNet:
         L['out'].dgrad(dpre, N, h.grad, accumulate=not h.first_write())
         for d in (0, 1, 2, 3):
             self._block_bwd(ar, 'dec%d' % d, ctx['dec%d' % d], N)
+            if self.attention_gate:
+                self._gate_bwd(ar, d, ctx['dec%d' % d], N)
             yield
         # bridge
         b = ctx['bridge']

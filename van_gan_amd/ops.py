@@ -68,7 +68,7 @@ class DryRun:
     pointers: a pointer only says whether it is set), enough to rebuild the call with random contents."""
 
     _CALLS = ('vg_actnorm_bwd', 'vg_actnorm_bwd_stats', 'vg_actnorm_bwd_apply', 'vg_actnorm_bwd_apply2', 'vg_concat_bwd', 'vg_affine_add',
-              'vg_in_finalize', 'vg_stem_short_fwd', 'vg_stem_short_bwd', 'vg_tanh_bwd')
+              'vg_in_finalize', 'vg_stem_short_fwd', 'vg_stem_short_bwd', 'vg_tanh_bwd', 'vg_attn_gate_fwd', 'vg_attn_gate_bwd')
     _ANB_FIELDS = ('N', 'D', 'H', 'W', 'C', 'g_padded', 'f32', 'x_f32', 'c_x0', 'x0_shift', 'act', 'norm', 'alias_n0', 'alias_shift',
                    'pgrad_n', 'dx_f32', 'accumulate', 'dx_cstride', 'dx_coff')
 
@@ -95,6 +95,10 @@ class DryRun:
             return (('N', a[1]), ('S', a[2]), ('C', a[3]), ('round16', a[8]), ('G', a[12]))
         if name == 'vg_stem_short_bwd':
             return (('g_f32', a[1]), ('N', a[3]), ('S', a[4]), ('C', a[5]), ('round16', a[9]), ('has_dgamma', int(bool(a[11]))), ('G', a[14]))
+        if name == 'vg_attn_gate_fwd':
+            return (('N', a[6]), ('D', a[7]), ('H', a[8]), ('W', a[9]), ('Cs', a[10]), ('Ci', a[11]), ('f32', a[12]))
+        if name == 'vg_attn_gate_bwd':
+            return (('N', a[7]), ('D', a[8]), ('H', a[9]), ('W', a[10]), ('Cs', a[11]), ('Ci', a[12]), ('f32', a[13]), ('acc', a[15]))
         assert name == 'vg_tanh_bwd'
         return (('n', a[3]),)
 
@@ -1427,6 +1431,24 @@ def affine_add(a, a_scale, a_shift, a_act, b, b_scale, b_shift, N, S, C_, out):
     """out = act(a * a_scale + a_shift) + (b * b_scale + b_shift)   (vg_affine_add: the residual Add of the ResNet generator)"""
     check(lib.vg_affine_add(_p(a), _p(a_scale), _p(a_shift), a_act, _p(b), _p(b_scale), _p(b_shift), N, S, C_, _p(out),
                             int(out.dtype == torch.float32), stream()), 'vg_affine_add')
+
+
+def attn_gate_fwd(skip, phi, w_theta, b_theta, w_psi, b_psi, dims, Cs, Ci, gated, h, sums):
+    """The decoder's attention gate (vg_attn_gate_fwd): gated = skip * sigmoid(relu(skip . w_theta + b_theta + phi[parent]) . w_psi + b_psi).
+    skip / gated [N, D, H, W, Cs], phi [N, D/2, H/2, W/2, Ci] (the low-resolution tensor's 1x1x1 convolution, bias included), h fp32
+    [N, D, H, W] (kept for the backward), sums [STRIPES, N, Cs, 2] += the statistics of the stored gated tensor."""
+    N, D, H, W = dims
+    check(lib.vg_attn_gate_fwd(_p(skip), _p(phi), _p(w_theta), _p(b_theta), _p(w_psi), _p(b_psi), N, D, H, W, Cs, Ci,
+                               int(skip.dtype == torch.float32), _p(gated), _p(h), _p(sums), stream()), 'vg_attn_gate_fwd')
+
+
+def attn_gate_bwd(dg, skip, h, phi, w_theta, b_theta, w_psi, dims, Cs, Ci, dskip, accumulate, dphi, dw_theta, db_theta, dw_psi, db_psi):
+    """Backward of attn_gate_fwd (vg_attn_gate_bwd): dskip (= or +=, `accumulate`) dg * h + dq . w_theta^T, dphi = dq summed over the
+    8 children of each low-resolution voxel, and the four parameter gradients ADDED; theta / q are recomputed."""
+    N, D, H, W = dims
+    check(lib.vg_attn_gate_bwd(_p(dg), _p(skip), _p(h), _p(phi), _p(w_theta), _p(b_theta), _p(w_psi), N, D, H, W, Cs, Ci,
+                               int(skip.dtype == torch.float32), _p(dskip), int(bool(accumulate)), _p(dphi), _p(dw_theta), _p(db_theta),
+                               _p(dw_psi), _p(db_psi), stream()), 'vg_attn_gate_bwd')
 
 
 def tanh_bwd(dy, y, dpre):

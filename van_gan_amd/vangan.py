@@ -113,8 +113,11 @@ class VanGan:
                  beta_1: float = 0.5, beta_2: float = 0.9, clipnorm: float = 100.0, layer_noise: float = 0.1,
                  dropout_rate: float = 0.2, skel_iters: int = 15, output_dir: Optional[str] = None,
                  process_group=None, arena_bytes: Optional[int] = None, precision: str = 'bf16', generator: str = 'resUnet',
-                 wasserstein: bool = False, spectral_norm: bool = False):
-        """spectral_norm=True: the discriminators of get_discriminator(use_SN=True) (discriminator.py:16,54-61,86,100): the four wrapped
+                 wasserstein: bool = False, spectral_norm: bool = False, attention_gate: bool = False):
+        """attention_gate=True: both generators are ResUNet(use_attention_gate=True) (resunet_model.py:152,178-179): every decoder level
+        gates its skip tensor (nets.ResUNet); 24 more tensors / 132 004 more parameters per generator.  Only with
+        generator='resUnet'.
+        spectral_norm=True: the discriminators of get_discriminator(use_SN=True) (discriminator.py:16,54-61,86,100): the four wrapped
         convolutions are spectrally normalised, no InstanceNorm.  Every train step projects each wrapped kernel twice (the reference
         applies a discriminator to the real and to the fake batch: two training calls of the wrapper) before the discriminator's
         [real; fake] application; test_step / generate never project.  Combines with wasserstein=True.  DESIGN.md section 8.
@@ -131,6 +134,9 @@ class VanGan:
         self.generator = generator                # both generators of one engine have the same architecture
         self.wasserstein = bool(wasserstein)
         self.spectral_norm = bool(spectral_norm)
+        self.attention_gate = bool(attention_gate)
+        if self.attention_gate and generator != 'resUnet':
+            raise ValueError("attention_gate=True is an option of the ResUNet generator (resunet_model.py:152): generator must be 'resUnet'")
         self.precision = precision
         self.dtype = torch.bfloat16 if precision == 'bf16' else torch.float32
         self.device = torch.device(device)
@@ -166,14 +172,15 @@ class VanGan:
         self.rng_offset = 0                       # Philox counter; persisted in the checkpoint
         self.stores: Dict[str, ParamStore] = {}
         for i, name in enumerate(NETS):
-            gspecs = gen_param_specs() if generator == 'resUnet' else resnet_param_specs()
+            gspecs = gen_param_specs(self.attention_gate) if generator == 'resUnet' else resnet_param_specs()
             n_patch = (self.dims[0] // 8) * (self.dims[1] // 8) * (self.dims[2] // 8) if self.wasserstein else 0
             st = ParamStore(gspecs if name.startswith('gen') else disc_param_specs(n_patch, self.spectral_norm), self.device)
             init_reference(st, seed + i)
             self.stores[name] = st
+        gkw = dict(attention_gate=True) if self.attention_gate else {}
         GenNet = ResUNet if generator == 'resUnet' else ResNetGenerator
-        self.gen_IS = GenNet(self.stores['gen_IS'], self.dims, self.dtype)
-        self.gen_SI = GenNet(self.stores['gen_SI'], self.dims, self.dtype)
+        self.gen_IS = GenNet(self.stores['gen_IS'], self.dims, self.dtype, **gkw)
+        self.gen_SI = GenNet(self.stores['gen_SI'], self.dims, self.dtype, **gkw)
         self.disc_I = PatchGAN(self.stores['disc_I'], self.dims, self.dtype, spectral_norm=self.spectral_norm)
         self.disc_S = PatchGAN(self.stores['disc_S'], self.dims, self.dtype, spectral_norm=self.spectral_norm)
         self.nets = {'gen_IS': self.gen_IS, 'gen_SI': self.gen_SI, 'disc_I': self.disc_I, 'disc_S': self.disc_S}
@@ -1032,7 +1039,8 @@ class VanGan:
             net = self._fp16_nets.get(gen)
             if net is None:
                 GenNet = ResUNet if self.generator == 'resUnet' else ResNetGenerator
-                net = self._fp16_nets[gen] = GenNet(self.stores[gen], self.dims, torch.float16)
+                net = self._fp16_nets[gen] = GenNet(self.stores[gen], self.dims, torch.float16,
+                                                    **(dict(attention_gate=True) if self.attention_gate else {}))
             net.pack()
         return net
 
@@ -1076,6 +1084,12 @@ class VanGan:
             return False
         ck = torch.load(path, map_location='cpu')
         for k, s in self.stores.items():         # nothing is loaded from a checkpoint of another configuration
+            if k.startswith('gen') and self.generator == 'resUnet' and ck[k]['w'].numel() != s.w.numel():
+                gated, plain = (sum(math.prod(sh) for _, sh, _ in gen_param_specs(a)) for a in (True, False))
+                if {ck[k]['w'].numel(), s.w.numel()} == {gated, plain}:
+                    raise ValueError('%s: %s was written %s the attention gate (%d weights), this engine is built %s it (%d weights)'
+                                     % (path, k, 'with' if ck[k]['w'].numel() == gated else 'without', ck[k]['w'].numel(),
+                                        'with' if self.attention_gate else 'without', s.w.numel()))
             has = 'sn_u' in ck[k]
             if has != bool(s.state.numel()) or ck[k]['w'].numel() != s.w.numel() or (has and ck[k]['sn_u'].numel() != s.state.numel()):
                 raise ValueError('%s: %s was written %s spectral normalisation (%d weights), this engine is built %s it (%d weights)'
