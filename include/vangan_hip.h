@@ -399,6 +399,18 @@ int vg_mse(const float* a, const float* b, int64_t n, float* acc, float gscale, 
  * acc[0] += sum (target - x)^2 ; gx (+)= gscale * 2 (x - target); x bf16 or f32 */
 int vg_mse_const(const void* x, int x_f32, float target, int64_t n, float* acc, float gscale, float* gx,
                  int accumulate, vg_stream_t stream);
+/* Selectable cycle terms MAE / MSE / L4 (loss_functions.py:41-84,177-184), p in {1, 2, 4} (anything else: VG_EINVAL):
+ * acc[0] += sum |b-a|^p ; gb (+)= gscale * p * |d|^(p-1) * sign(d), d = b-a, sign(0) = 0 (TP: tf.abs has gradient 0 at 0);
+ * gb == NULL: forward only.  p = 2 gives vg_mse's values. */
+int vg_lp_loss(const float* a, const float* b, int64_t n, int p, float* acc, float gscale, float* gb, int accumulate,
+               vg_stream_t stream);
+/* Selectable adversarial terms on patch logits (loss_functions.py:275-286,309-322 with from_logits=True); x bf16 or f32, target z in
+ * {0, 1}, kind in {0, 1} (anything else: VG_EINVAL).  TP, restated from Keras 2.10:
+ *   kind 0  BinaryCrossentropy(from_logits=True)      = max(x,0) - x z + log1p(exp(-|x|))
+ *   kind 1  BinaryFocalCrossentropy(from_logits=True) = (1 - p_t)^2 * bce, p_t = z s + (1-z)(1-s), s = sigmoid(x)  (gamma 2, no balancing)
+ * acc[0] += sum loss ; gx (+)= gscale * d loss / d x (closed forms, finite for every finite logit); gx == NULL: forward only. */
+int vg_logit_loss(const void* x, int x_f32, float target, int kind, int64_t n, float* acc, float gscale, float* gx,
+                  int accumulate, vg_stream_t stream);
 /* SSIM (loss_functions.py:86-117): acc[0] += sum (1-ssim); part[3][B][S] = dL/d(mu_p, E[pp], E[tp]) */
 int vg_ssim_fwd(const float* t, const float* p, int B, int D, int H, int W, float* acc, float* part,
                 vg_stream_t stream);

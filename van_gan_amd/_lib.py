@@ -118,6 +118,8 @@ _SIGS = {
     'vg_bce': ([c_void_p, c_void_p, c_i64, c_void_p, c_float, c_void_p, c_int, c_void_p], c_int),
     'vg_mse': ([c_void_p, c_void_p, c_i64, c_void_p, c_float, c_void_p, c_int, c_void_p], c_int),
     'vg_mse_const': ([c_void_p, c_int, c_float, c_i64, c_void_p, c_float, c_void_p, c_int, c_void_p], c_int),
+    'vg_lp_loss': ([c_void_p, c_void_p, c_i64, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p], c_int),
+    'vg_logit_loss': ([c_void_p, c_int, c_float, c_int, c_i64, c_void_p, c_float, c_void_p, c_int, c_void_p], c_int),
     'vg_ssim_fwd': ([c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     'vg_ssim_bwd': ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p], c_int),
     'vg_soft_skel_fwd': ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),

@@ -29,12 +29,18 @@ KNOWN_GENERATORS = ('resnet', 'resUnet', 'vnet')       # vangan.py:88-124, 127-1
 
 def engine_kwargs_from_args(args, lambda_cycle=10.0, lambda_identity=5, lambda_reconstruction=5, lambda_topology=5,
                             gen_i2s='resnet', gen_s2i='resnet', semi_supervised=False, wasserstein=False,
-                            ncritic=5, gp_weight=10.0, use_SN=False, use_attention_gate=False) -> Dict:
+                            ncritic=5, gp_weight=10.0, use_SN=False, use_attention_gate=False, *, cycle_loss_SIS='bce',
+                            cycle_loss_ISI='mse', gan_loss=None) -> Dict:
     """Validate the reference's constructor arguments and translate them into the engine's (pure host logic).
     use_SN: get_discriminator's own switch (discriminator.py:16), which the reference's VanGan does not expose -- it hard-codes
     use_SN=False at vangan.py:175,188; True maps to the engine's spectral_norm=True.
     use_attention_gate: ResUNet's own switch (resunet_model.py:152), hard-coded to False at vangan.py:118,157; True maps to the engine's
-    attention_gate=True and needs the 'resUnet' generators."""
+    attention_gate=True and needs the 'resUnet' generators.
+    cycle_loss_SIS / cycle_loss_ISI / gan_loss: the `typ` arguments of cycle_loss and generator_loss_fn / discriminator_loss_fn
+    (loss_functions.py:163-190,255-322), which the reference's VanGan hard-codes at vangan.py:302,306,329-332 (the defaults here);
+    van_gan_amd.losstypes names the values.  Unknown names raise ValueError, and so does gan_loss together with wasserstein."""
+    from .losstypes import check_loss_types
+    check_loss_types(cycle_loss_SIS, cycle_loss_ISI, gan_loss, bool(wasserstein))
     if gen_i2s not in KNOWN_GENERATORS:
         raise ValueError('IS Generator type not recognised')          # vangan.py:124
     if gen_s2i not in KNOWN_GENERATORS:
@@ -70,7 +76,10 @@ def engine_kwargs_from_args(args, lambda_cycle=10.0, lambda_identity=5, lambda_r
                 # frozen at trace time: ncritic / gp_weight are accepted and inert
                 **(dict(wasserstein=True, lr=1e-4, beta_1=0.0, beta_2=0.9, clipnorm=0.0) if wasserstein else {}),
                 **(dict(spectral_norm=True) if use_SN else {}),
-                **(dict(attention_gate=True) if use_attention_gate else {}))
+                **(dict(attention_gate=True) if use_attention_gate else {}),
+                **(dict(cycle_loss_SIS=cycle_loss_SIS) if cycle_loss_SIS != 'bce' else {}),
+                **(dict(cycle_loss_ISI=cycle_loss_ISI) if cycle_loss_ISI != 'mse' else {}),
+                **(dict(gan_loss=gan_loss) if gan_loss is not None else {}))
 
 
 def to_device_volume(t, device) -> torch.Tensor:
@@ -197,15 +206,21 @@ class VanGan:
 
     def __init__(self, args, strategy=None, lambda_cycle=10.0, lambda_identity=5, lambda_reconstruction=5,
                  lambda_topology=5, gen_i2s='resnet', gen_s2i='resnet', semi_supervised=False, wasserstein=False,
-                 ncritic=5, gp_weight=10.0, *, use_SN: bool = False, use_attention_gate: bool = False, device: str = 'cuda:0', process_group=None, seed: int = 0,
-                 engine_factory: Optional[Callable] = None, **engine_kw):
+                 ncritic=5, gp_weight=10.0, *, use_SN: bool = False, use_attention_gate: bool = False,
+                 cycle_loss_SIS: str = 'bce', cycle_loss_ISI: str = 'mse', gan_loss: Optional[str] = None, device: str = 'cuda:0', process_group=None,
+                 seed: int = 0, engine_factory: Optional[Callable] = None, **engine_kw):
         """use_SN (keyword extension behind the reference's arguments): spectrally normalised discriminators,
         get_discriminator(use_SN=True) of discriminator.py:16,54-61,86,100.  The reference's VanGan cannot reach them -- it hard-codes
         use_SN=False at vangan.py:175,188.  Combines with wasserstein=True.
         use_attention_gate (the same kind of extension): both generators are ResUNet(use_attention_gate=True) (resunet_model.py:152,
-        178-179), which the reference's VanGan hard-codes to False at vangan.py:118,157; needs gen_i2s == gen_s2i == 'resUnet'."""
+        178-179), which the reference's VanGan hard-codes to False at vangan.py:118,157; needs gen_i2s == gen_s2i == 'resUnet'.
+        cycle_loss_SIS / cycle_loss_ISI / gan_loss (likewise): the loss types the reference's loss functions take as `typ` and its VanGan
+        hard-codes at vangan.py:302,306,329-332 -- 'mae' | 'mse' | 'L4' | 'bce' for the two cycle terms (real_S / cycled_S, result key
+        cycle_gen_SIS_loss; real_I / cycled_I, cycle_gen_ISI_loss), None (LSGAN) | 'bce' | 'bfce' for the adversarial terms."""
         kw = engine_kwargs_from_args(args, lambda_cycle, lambda_identity, lambda_reconstruction, lambda_topology, gen_i2s,
-                                     gen_s2i, semi_supervised, wasserstein, ncritic, gp_weight, use_SN, use_attention_gate)
+                                     gen_s2i, semi_supervised, wasserstein, ncritic, gp_weight, use_SN, use_attention_gate,
+                                     cycle_loss_SIS=cycle_loss_SIS, cycle_loss_ISI=cycle_loss_ISI, gan_loss=gan_loss)
+        self.cycle_loss_SIS, self.cycle_loss_ISI, self.gan_loss = cycle_loss_SIS, cycle_loss_ISI, gan_loss
         self.use_SN = bool(use_SN)
         self.use_attention_gate = bool(use_attention_gate)
         kw.update(engine_kw)

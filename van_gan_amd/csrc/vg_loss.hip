@@ -203,6 +203,114 @@ extern "C" int vg_mse_const(const void* x, int x_f32, float target, int64_t n, f
                        gscale, gx, accumulate);
     return vg_check_launch();
 }
+// ---- selectable cycle terms: MAE / MSE / L4 (loss_functions.py:41-84,177-184) ----
+// sum |d|^P and gscale * P * |d|^(P-1) * sign(d), d = b - a, sign(0) = 0 (TP: tf.abs has gradient 0 at 0).  P = 2 evaluates the
+// gradient as vg_mse does ((gscale * 2) * d): the same values.
+template <int P>
+__device__ __forceinline__ float lp_term(float d, float gscale, float& g) {
+    if (P == 1) { g = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f); return fabsf(d); }
+    if (P == 2) { g = gscale * 2.f * d; return d * d; }
+    const float d2 = d * d;
+    g = gscale * 4.f * (d2 * d);
+    return d2 * d2;
+}
+// The bytes of mse_kernel (two reads, one optional read-modify-write) in another launch shape, the one dot_sums_kernel learnt: 16-byte
+// loads and stores where the three pointers are aligned (scalar walk otherwise, and for the n % 4 tail), 4 iterations per thread at
+// 128^3 instead of 16, <= 511 blocks, one float atomic per block.  Measured beside vg_mse: DESIGN.md section 3.10 (about 11 % faster).
+template <int P>
+__global__ __launch_bounds__(256) void lp_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n, float* acc, float gscale,
+                                                      float* gb, int accum) {
+    __shared__ float sm[4];
+    float s = 0.f;
+    const int64_t n4 = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)gb) & 15) == 0) ? n >> 2 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 x = ((const f32x4*)a)[i], y = ((const f32x4*)b)[i];
+        f32x4 g;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { float gj; s += lp_term<P>(y[j] - x[j], gscale, gj); g[j] = gj; }
+        if (gb) { if (accum) g += ((const f32x4*)gb)[i]; ((f32x4*)gb)[i] = g; }
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float g;
+        s += lp_term<P>(b[i] - a[i], gscale, g);
+        if (gb) gb[i] = accum ? gb[i] + g : g;
+    }
+    s = block_sum(s, sm);
+    if (threadIdx.x == 0) atomicAdd(acc, s);
+}
+extern "C" int vg_lp_loss(const float* a, const float* b, int64_t n, int p, float* acc, float gscale, float* gb, int accumulate,
+                          vg_stream_t stream) {
+    vg_begin();
+    if (!a || !b || !acc || n < 1 || (p != 1 && p != 2 && p != 4)) return VG_EINVAL;
+    const dim3 grid(lblocks(n, 4096) > 511 ? 511 : lblocks(n, 4096));
+    hipStream_t s = (hipStream_t)stream;
+    if (p == 1) hipLaunchKernelGGL(lp_loss_kernel<1>, grid, dim3(256), 0, s, a, b, n, acc, gscale, gb, accumulate);
+    else if (p == 2) hipLaunchKernelGGL(lp_loss_kernel<2>, grid, dim3(256), 0, s, a, b, n, acc, gscale, gb, accumulate);
+    else hipLaunchKernelGGL(lp_loss_kernel<4>, grid, dim3(256), 0, s, a, b, n, acc, gscale, gb, accumulate);
+    return vg_check_launch();
+}
+// ---- selectable adversarial terms on patch logits (loss_functions.py:275-286,309-322, from_logits=True), target z in {0, 1} ----
+// TP (Keras 2.10, restated; TensorFlow is not available to check against):
+//   KIND 0  BinaryCrossentropy(from_logits=True)      = max(x, 0) - x z + log1p(exp(-|x|))                      d/dx = s - z
+//   KIND 1  BinaryFocalCrossentropy(from_logits=True), gamma = 2, no class balancing = (1 - p_t)^2 * bce, p_t = z s + (1 - z)(1 - s)
+//           z = 1: (1 - s)^2 softplus(-x),  d/dx = -(1 - s)^3 - 2 s (1 - s)^2 softplus(-x)
+//           z = 0: s^2 softplus(x),         d/dx =  s^3 + 2 s^2 (1 - s) softplus(x)
+// with s = sigmoid(x).  s and 1 - s both come from e = exp(-|x|) (never 1 - s by subtraction, never log(1 - s)): finite for every
+// finite logit.
+template <int KIND>
+__device__ __forceinline__ float logit_term(float x, bool one, float& g) {
+    const float e = expf(-fabsf(x));
+    const float r = 1.f / (1.f + e);
+    const float s = x >= 0.f ? r : e * r, c = x >= 0.f ? e * r : r;        // sigmoid(x), 1 - sigmoid(x)
+    const float l1p = log1pf(e);
+    const float sp = one ? fmaxf(-x, 0.f) + l1p : fmaxf(x, 0.f) + l1p;      // softplus(-x) / softplus(x) = the BCE term
+    if (KIND == 0) { g = one ? -c : s; return sp; }
+    if (one) { g = -(c * c * c) - 2.f * s * c * c * sp; return c * c * sp; }
+    g = s * s * s + 2.f * s * s * c * sp;
+    return s * s * sp;
+}
+template <int KIND, typename T>
+__global__ __launch_bounds__(256) void logit_loss_kernel(const T* __restrict__ x, int one, int64_t n, float* acc, float gscale, float* gx, int accum) {
+    __shared__ float sm[4];
+    float s = 0.f;
+    // eight logits per step where the pointers allow 16-byte accesses (bf16: one load; fp32: two), scalar walk otherwise and for the tail
+    const int64_t n8 = ((((uintptr_t)x | (uintptr_t)gx) & 15) == 0) ? n >> 3 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+        float v[8], g[8];
+        load8<T>(x + 8 * i, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { s += logit_term<KIND>(v[j], one != 0, g[j]); g[j] *= gscale; }
+        if (gx) {
+            if (accum) {
+                float o[8]; load8<float>(gx + 8 * i, o);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) g[j] += o[j];
+            }
+            store8<float>(gx + 8 * i, g);
+        }
+    }
+    for (int64_t i = 8 * n8 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float g;
+        s += logit_term<KIND>(ld1<T>(x + i), one != 0, g);
+        g *= gscale;
+        if (gx) gx[i] = accum ? gx[i] + g : g;
+    }
+    s = block_sum(s, sm);
+    if (threadIdx.x == 0) atomicAdd(acc, s);
+}
+extern "C" int vg_logit_loss(const void* x, int x_f32, float target, int kind, int64_t n, float* acc, float gscale, float* gx,
+                             int accumulate, vg_stream_t stream) {
+    vg_begin();
+    if (!x || !acc || n < 1 || (target != 0.f && target != 1.f) || (kind != 0 && kind != 1)) return VG_EINVAL;
+    const dim3 grid(lblocks(n, 2048) > 255 ? 255 : lblocks(n, 2048));      // (one float atomic per block on one address)
+    hipStream_t s = (hipStream_t)stream;
+    const int one = target == 1.f;
+#define VG_LOGIT_LAUNCH(K, T) hipLaunchKernelGGL((logit_loss_kernel<K, T>), grid, dim3(256), 0, s, (const T*)x, one, n, acc, gscale, gx, accumulate)
+    if (kind == 0) { if (x_f32) VG_LOGIT_LAUNCH(0, float); else VG_LOGIT_LAUNCH(0, bf16_t); }
+    else           { if (x_f32) VG_LOGIT_LAUNCH(1, float); else VG_LOGIT_LAUNCH(1, bf16_t); }
+#undef VG_LOGIT_LAUNCH
+    return vg_check_launch();
+}
 // (First version: 2 048 blocks of scalar loads, three float atomics per block on ONE cache line -- 82 us for two 8-MB volumes, all of it
 // the serialised atomics.  Now <= 255 blocks, 16-byte loads.)
 __global__ void dot_sums_kernel(const float* a, const float* b, int64_t n, float* sums3) {

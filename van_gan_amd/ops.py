@@ -1483,6 +1483,21 @@ def mse_const(x, target, acc, gscale=0.0, gx=None, accumulate=False):
                            int(accumulate), stream()), 'vg_mse_const')
 
 
+def lp_loss(a, b, p, acc, gscale=0.0, gb=None, accumulate=False):
+    """acc += sum |b - a|^p, gb (+)= gscale * p * |d|^(p-1) * sign(d); p in {1, 2, 4} (MAE / MSE / L4 of loss_functions.py:41-84)."""
+    check(lib.vg_lp_loss(_p(a), _p(b), a.numel(), int(p), _p(acc), gscale, _p(gb), int(accumulate), stream()), 'vg_lp_loss')
+
+
+LOGIT_BCE, LOGIT_FOCAL = 0, 1
+
+
+def logit_loss(x, target, kind, acc, gscale=0.0, gx=None, accumulate=False):
+    """acc += sum loss(target, x) over patch logits (fp32 or the engine's 16-bit storage), gx (+)= gscale * d loss / d x; kind LOGIT_BCE /
+    LOGIT_FOCAL = Keras BinaryCrossentropy / BinaryFocalCrossentropy with from_logits=True (TP), target 0 or 1."""
+    check(lib.vg_logit_loss(_p(x), int(x.dtype == torch.float32), target, int(kind), x.numel(), _p(acc), gscale, _p(gx),
+                            int(accumulate), stream()), 'vg_logit_loss')
+
+
 def ssim_fwd(t, p, dims, acc, part):
     B, D, H, W = dims
     check(lib.vg_ssim_fwd(_p(t), _p(p), B, D, H, W, _p(acc), _p(part), stream()), 'vg_ssim_fwd')

@@ -17,6 +17,7 @@ import torch
 
 from . import ops, roctx
 from .dist import GradSync
+from .losstypes import LP_ORDER, check_loss_types
 from .nets import (pair_ctx, PatchGAN, ParamStore, ResNetGenerator, ResUNet, disc_param_specs, gen_param_specs, init_reference,
                    resnet_param_specs)
 from .ops import Arena
@@ -113,8 +114,15 @@ class VanGan:
                  beta_1: float = 0.5, beta_2: float = 0.9, clipnorm: float = 100.0, layer_noise: float = 0.1,
                  dropout_rate: float = 0.2, skel_iters: int = 15, output_dir: Optional[str] = None,
                  process_group=None, arena_bytes: Optional[int] = None, precision: str = 'bf16', generator: str = 'resUnet',
-                 wasserstein: bool = False, spectral_norm: bool = False, attention_gate: bool = False):
-        """attention_gate=True: both generators are ResUNet(use_attention_gate=True) (resunet_model.py:152,178-179): every decoder level
+                 wasserstein: bool = False, spectral_norm: bool = False, attention_gate: bool = False,
+                 cycle_loss_SIS: str = 'bce', cycle_loss_ISI: str = 'mse', gan_loss: Optional[str] = None):
+        """cycle_loss_SIS / cycle_loss_ISI: the `typ` of cycle_loss (loss_functions.py:163-190) for the term between real_S and cycled_S
+        (the reference's cycle_loss_I, result key cycle_gen_SIS_loss) and between real_I and cycled_I (cycle_loss_S, cycle_gen_ISI_loss):
+        'mae' (the reference's typ=None), 'mse', 'L4' on the raw volumes through reduce_mean(axis=list), or 'bce' on the min-max
+        normalised volumes through reduce_mean(axis=None).  gan_loss: the `typ` of generator_loss_fn / discriminator_loss_fn (:255-322,
+        from_logits=True): None (LSGAN), 'bce' or 'bfce' (TP: Keras BinaryCrossentropy / BinaryFocalCrossentropy); not with
+        wasserstein=True.  The defaults are what the reference's VanGan hard-codes (vangan.py:302,306,329-332).  DESIGN.md section 3.10.
+        attention_gate=True: both generators are ResUNet(use_attention_gate=True) (resunet_model.py:152,178-179): every decoder level
         gates its skip tensor (nets.ResUNet); 24 more tensors / 132 004 more parameters per generator.  Only with
         generator='resUnet'.
         spectral_norm=True: the discriminators of get_discriminator(use_SN=True) (discriminator.py:16,54-61,86,100): the four wrapped
@@ -131,6 +139,7 @@ class VanGan:
             raise ValueError("precision must be 'bf16' (product path) or 'fp32' (exact-parity mode)")
         if generator not in ('resUnet', 'resnet'):
             raise ValueError("generator must be 'resUnet' (default, vangan.py:113-123) or 'resnet' (vangan.py:88-97)")
+        self.cycle_loss_SIS, self.cycle_loss_ISI, self.gan_loss = check_loss_types(cycle_loss_SIS, cycle_loss_ISI, gan_loss, bool(wasserstein))
         self.generator = generator                # both generators of one engine have the same architecture
         self.wasserstein = bool(wasserstein)
         self.spectral_norm = bool(spectral_norm)
@@ -472,7 +481,11 @@ class VanGan:
                 ncS = ar.alloc(vol, f32)
                 ops.minmax(cyc_S, B, S, mmcS); ops.minmax_apply(cyc_S, mmcS, B, S, ncS)
             g_ncS = ar.alloc(vol, f32) if do_backward else None
-            ops.bce(nS, ncS, acc[0:1], self.lambda_cycle / (B * S * gbs), g_ncS, accumulate=False)
+            sis_bce = self.cycle_loss_SIS == 'bce'
+            if sis_bce:
+                ops.bce(nS, ncS, acc[0:1], self._cycle_scale('SIS', B, S), g_ncS, accumulate=False)
+            elif not do_backward:                # MAE / MSE / L4 on the RAW volumes (loss_functions.py:177-184); the min-max stays for clDice
+                ops.lp_loss(rS, cyc_S, LP_ORDER[self.cycle_loss_SIS], acc[0:1])
             if not skel_fwd_on_a:
                 imgs_p, skels_p = ar.alloc((it + 2,) + vol, f32), ar.alloc((it + 1,) + vol, f32)
                 # the predicted skeleton is differentiated: its forward pass files delta and the pooling arg-extrema codes (6 B per voxel and step)
@@ -487,11 +500,15 @@ class VanGan:
             ops.cldice_coef(sums, self.lambda_topology / self.n_devices, 0.5, coef)
             def cldice_backward():
                 gskel = ar.alloc(vol, f32)
-                ops.cldice_grads(nS, skel_t, coef, gskel, g_ncS, accumulate=True)
+                ops.cldice_grads(nS, skel_t, coef, gskel, g_ncS, accumulate=sis_bce)      # (without the BCE term: the first writer of g_ncS)
                 work = ar.alloc((4,) + vol, f32)
                 ops.soft_skel_bwd(imgs_p, skels_p, gskel, dims4, it, work, g_ncS, aux_p)
                 tmp2 = ar.alloc((B, 2), f32, zero=True)
                 ops.minmax_bwd(cyc_S, ncS, g_ncS, mmcS, B, S, tmp2, gS2[B:])
+                if not sis_bce:
+                    # the raw-volume cycle term adds its gradient DIRECTLY to d cycled_S, behind the min-max backward that writes the
+                    # buffer -- same function, so same stream, whichever lane VG_SKEL_BWD_A puts this on (no event of its own)
+                    ops.lp_loss(rS, cyc_S, LP_ORDER[self.cycle_loss_SIS], acc[0:1], self._cycle_scale('SIS', B, S), gS2[B:], accumulate=True)
             g_cS = gS2[B:] if do_backward else None
             # VG_SKEL_BWD_A: the skeleton's backward (34 launches whose result only lane A's generator sweep consumes) on lane A, behind
             # an event of lane B's clDice forward -- lane B is the longer lane (tools/timeline.py: lane A ends 1.2 ms before it)
@@ -503,7 +520,11 @@ class VanGan:
 
         # ---- cycle MSE + SSIM reconstruction on cycled_I (loss_functions.py:179-180, 193-208) ----
         g_cI = gI2[B:] if do_backward else None
-        ops.mse(rI, cyc_I, acc[1:2], self.lambda_cycle / (S * gbs), g_cI, accumulate=False)
+        isi_bce = self.cycle_loss_ISI == 'bce'
+        if self.cycle_loss_ISI == 'mse':
+            ops.mse(rI, cyc_I, acc[1:2], self.lambda_cycle / (S * gbs), g_cI, accumulate=False)
+        elif not isi_bce:
+            ops.lp_loss(rI, cyc_I, LP_ORDER[self.cycle_loss_ISI], acc[1:2], self._cycle_scale('ISI', B, S), g_cI, accumulate=False)
         mmI, mmcI = ar.alloc((B, 4), f32), ar.alloc((B, 4), f32)
         nI, ncI = ar.alloc(vol, f32), ar.alloc(vol, f32)
         ops.minmax(rI, B, S, mmI); ops.minmax_apply(rI, mmI, B, S, nI)
@@ -513,10 +534,19 @@ class VanGan:
         if do_backward:
             g_ncI = ar.alloc(vol, f32)
             ops.ssim_bwd(nI, ncI, part, dims4, self.lambda_reconstruction / (B * S * gbs), g_ncI, accumulate=False)
-            g_tmp = ar.alloc(vol, f32)
-            tmp2b = ar.alloc((B, 2), f32, zero=True)
-            ops.minmax_bwd(cyc_I, ncI, g_ncI, mmcI, B, S, tmp2b, g_tmp)
-            ops.axpby(g_tmp, 1.0, None, 0.0, g_cI, accumulate=True)
+            if isi_bce:
+                # BCE on the normalised volumes the SSIM block already holds (loss_functions.py:186-190): its gradient joins SSIM's in
+                # g_ncI, and the ONE min-max backward is the first and only writer of d cycled_I
+                ops.bce(nI, ncI, acc[1:2], self._cycle_scale('ISI', B, S), g_ncI, accumulate=True)
+                tmp2b = ar.alloc((B, 2), f32, zero=True)
+                ops.minmax_bwd(cyc_I, ncI, g_ncI, mmcI, B, S, tmp2b, g_cI)
+            else:
+                g_tmp = ar.alloc(vol, f32)
+                tmp2b = ar.alloc((B, 2), f32, zero=True)
+                ops.minmax_bwd(cyc_I, ncI, g_ncI, mmcI, B, S, tmp2b, g_tmp)
+                ops.axpby(g_tmp, 1.0, None, 0.0, g_cI, accumulate=True)
+        elif isi_bce:
+            ops.bce(nI, ncI, acc[1:2])
         self._mark('A cycle losses')
 
         # ---- discriminators on [real; fake] (vangan.py:315-319) and LSGAN losses (:329-332) ----
@@ -536,7 +566,8 @@ class VanGan:
             self.disc_S.project(2)
             self.disc_I.project(2)
         dS = self.disc_S.forward(ar, bufS, logS, nzS, dpS)                                  # lane A: needs fake_S
-        gd = 1.0 / (nps * gbs)
+        gd = self._adv_scale(B, nps)
+        adv = self._adv_term
         # upstream gradients at the patch logits, adjacent: [d critic loss (2B: real, fake); d generator loss (B: fake)] -- one 3B-sample
         # backward sweep per discriminator reads them as one tensor (VG_D_ONE_SWEEP)
         gS3 = ar.alloc((3 * B,) + tuple(logS.shape[1:]), f32) if do_backward else None
@@ -556,9 +587,9 @@ class VanGan:
         if self.wasserstein:
             w_terms('S', self.disc_S, logS, dpS, 9)
         else:
-            ops.mse_const(logS[B:], 1.0, acc[3:4], gd, gS_G)                                  # gen_IS_loss
-            ops.mse_const(logS[:B], 1.0, acc[5:6], 0.5 * gd, None if gS_D is None else gS_D[:B])
-            ops.mse_const(logS[B:], 0.0, acc[6:7], 0.5 * gd, None if gS_D is None else gS_D[B:])
+            adv(logS[B:], 1.0, acc[3:4], gd, gS_G)                                  # gen_IS_loss
+            adv(logS[:B], 1.0, acc[5:6], 0.5 * gd, None if gS_D is None else gS_D[:B])
+            adv(logS[B:], 0.0, acc[6:7], 0.5 * gd, None if gS_D is None else gS_D[B:])
         self._mark('A D_S fwd')
         if lane_b is not None:
             ops.wait_event(main, ev_fakeI)                                                       # fake_I comes from lane B's first generator
@@ -566,9 +597,9 @@ class VanGan:
         if self.wasserstein:
             w_terms('I', self.disc_I, logI, dpI, 11)
         else:
-            ops.mse_const(logI[B:], 1.0, acc[4:5], gd, gI_G)                                  # gen_SI_loss
-            ops.mse_const(logI[:B], 1.0, acc[7:8], 0.5 * gd, None if gI_D is None else gI_D[:B])
-            ops.mse_const(logI[B:], 0.0, acc[8:9], 0.5 * gd, None if gI_D is None else gI_D[B:])
+            adv(logI[B:], 1.0, acc[4:5], gd, gI_G)                                  # gen_SI_loss
+            adv(logI[:B], 1.0, acc[7:8], 0.5 * gd, None if gI_D is None else gI_D[:B])
+            adv(logI[B:], 0.0, acc[8:9], 0.5 * gd, None if gI_D is None else gI_D[B:])
         self._mark('A D fwd')
         if skel_bwd_on_a and _SKEL_BWD_A == 1:
             ops.wait_event(main, ev_cldice)
@@ -731,20 +762,39 @@ class VanGan:
         self._fwd_ctx = {'G_IS.a': c1, 'G_SI.a': c2, 'G_IS.b': c3, 'G_SI.b': c4, 'D_S': dS, 'D_I': dI}
         return B, S, nps
 
+    def _cycle_scale(self, which: str, B: int, S: int) -> float:
+        """lambda_cycle times what reduce_mean leaves of a SUM over the B * S voxels: MAE / MSE / L4 go through reduce_mean(axis=list) --
+        a mean per sample, summed, over the global batch size; the BCE term through reduce_mean(axis=None) -- the mean includes the batch
+        (loss_functions.py:7-22,177-190)."""
+        typ = self.cycle_loss_SIS if which == 'SIS' else self.cycle_loss_ISI
+        return self.lambda_cycle / ((B * S if typ == 'bce' else S) * float(self.global_batch_size))
+
+    def _adv_scale(self, B: int, nps: int) -> float:
+        """LSGAN: MSE = reduce_mean(axis=list) over the patch logits; 'bce' / 'bfce': reduce_mean(axis=None) (loss_functions.py:274,286,322)."""
+        return 1.0 / ((nps if self.gan_loss is None else B * nps) * float(self.global_batch_size))
+
+    def _adv_term(self, x, target, acc, gscale=0.0, gx=None):
+        """One adversarial term on patch logits: acc += sum loss(target, x), gx = gscale * d loss / d x."""
+        if self.gan_loss is None:
+            ops.mse_const(x, target, acc, gscale, gx)
+        else:
+            ops.logit_loss(x, target, ops.LOGIT_BCE if self.gan_loss == 'bce' else ops.LOGIT_FOCAL, acc, gscale, gx)
+
     def _results(self, B, S, nps) -> Dict[str, float]:
         a = self._acc.cpu().tolist()        # the only host sync of the step
         seg = float(self._coef[5].item())
         gbs = float(self.global_batch_size)
-        cyc_I = a[0] / (B * S * gbs) * self.lambda_cycle
-        cyc_S = a[1] / (S * gbs) * self.lambda_cycle
+        cyc_I = a[0] * self._cycle_scale('SIS', B, S)
+        cyc_S = a[1] * self._cycle_scale('ISI', B, S)
         rec = a[2] / (B * S * gbs) * self.lambda_reconstruction
         if self.wasserstein:            # -reduce_mean(D(fake)), -reduce_mean(D(real) - D(fake)): acc[9:11] = (sum z_real, sum z_fake) of D_S, [11:13] of D_I
             gIS, gSI = -a[10] / (B * gbs), -a[12] / (B * gbs)
             dS, dI = -(a[9] - a[10]) / (B * gbs), -(a[11] - a[12]) / (B * gbs)
         else:
-            gIS, gSI = a[3] / (nps * gbs), a[4] / (nps * gbs)
-            dS = 0.5 * (a[5] + a[6]) / (nps * gbs)
-            dI = 0.5 * (a[7] + a[8]) / (nps * gbs)
+            gd = self._adv_scale(B, nps)
+            gIS, gSI = a[3] * gd, a[4] * gd
+            dS = 0.5 * (a[5] + a[6]) * gd
+            dI = 0.5 * (a[7] + a[8]) * gd
         vals = [gIS + cyc_I + seg, gSI + cyc_S + rec, dI, dS, gIS, gSI, cyc_I, cyc_S, seg, rec]
         return dict(zip(RESULT_KEYS, vals))
 
