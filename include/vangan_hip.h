@@ -463,6 +463,21 @@ int vg_overlap_add(const float* win, int kx, int ky, int kz, int px, int py, int
                    int X, int Y, int Z, float* pred, float* cnt, vg_stream_t stream);
 int vg_divide_crop(const float* pred, const float* cnt, int X, int Y, int Z, int sx, int sy, int sz, int ox, int oy,
                    int oz, float* out, vg_stream_t stream);
+/* Batched forms for the blended / flip-averaged modes (beyond the reference; van_gan_amd/inference.py), fp32 in both storage builds.
+ * tab: device table of B rows of four int32 (x0, y0, z0, flip); flip bit 0 mirrors x (the first axis of the [X][Y][Z] volume), bit 1 y,
+ * bit 2 z:  f_a(i) = flip bit a ? k_a - 1 - i : i.  One launch per call, whatever B.
+ * vg_window_gather:  out[b][i][j][k] = vol[x0 + f_x(i)][y0 + f_y(j)][z0 + f_z(k)],  out [B][kx][ky][kz]  (a copy: bit-exact).
+ * vg_window_scatter: for every row b and every voxel px <= i < kx - px (likewise y, z; window coordinates in VOLUME orientation)
+ *   v = win[b][f_x(i)][f_y(j)][f_z(k)]  (un-flips the prediction),  w = (wx[i] * wy[j]) * wz[k]  (fp32; per-axis tables of k_a floats),
+ *   atomicAdd(pred[x0+i][y0+j][z0+k], w * v),  atomicAdd(cnt[...], w).  wx == wy == wz == NULL: w = 1, pred += v, what vg_overlap_add adds.
+ *   vg_divide_crop then divides by the summed weights.  Float atomics: the sums depend on arrival order in their last bits.
+ * VG_EINVAL (nothing launched): a NULL pointer, B < 1, k_a < 1, k_a > the volume extent, p_a < 0, k_a - 2 p_a < 1, one or two of the
+ * three weight tables.  The table is on the device and is the caller's to validate (origins in [0, extent - k_a], flip in 0..7); a row
+ * outside those ranges is skipped by the kernels and never dereferenced. */
+int vg_window_gather(const float* vol, int X, int Y, int Z, const int* tab, int B, int kx, int ky, int kz, float* out,
+                     vg_stream_t stream);
+int vg_window_scatter(const float* win, const int* tab, int B, int kx, int ky, int kz, int px, int py, int pz, const float* wx,
+                      const float* wy, const float* wz, int X, int Y, int Z, float* pred, float* cnt, vg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-tensor Adam with per-tensor clip-by-norm (tf.keras.optimizers.Adam(2e-4, 0.5, 0.9,

@@ -132,6 +132,8 @@ _SIGS = {
     'vg_dot_sums': ([c_void_p, c_void_p, c_i64, c_void_p, c_void_p], c_int),
     'vg_overlap_add': ([c_void_p] + [c_int] * 12 + [c_void_p, c_void_p, c_void_p], c_int),
     'vg_divide_crop': ([c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p], c_int),
+    'vg_window_gather': ([c_void_p, c_int, c_int, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p], c_int),
+    'vg_window_scatter': ([c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 3, c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),
