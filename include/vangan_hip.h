@@ -588,6 +588,45 @@ int vg_crop_augment(const float* vol, int X, int Y, int Z, int C, int x0, int y0
 int vg_crop_max(const float* vol, int X, int Y, int Z, int C, int x0, int y0, int z0, int px, int py, int pz,
                 float* out, vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Raw-volume preprocessing (preprocess_rsom_images, main.py:127-150, then min_max_norm and (x - 0.5) / 0.5 of process_tiff,
+ * preprocessing.py:179-185), restated; van_gan_amd/preprocess.py, csrc/vg_preproc.hip, DESIGN.md section 3.12.  The same code in both
+ * storage builds.  vol: [X][Y][Z] with Z innermost, nxy = X * Y, n = nxy * Z; dtype is one of VG_PP_U8 / VG_PP_U16 / VG_PP_F32 (a raw
+ * 8- or 16-bit stack is read as it is).  Every entry only enqueues, allocates nothing and checks its arguments on the host before any
+ * launch (VG_EINVAL, nothing launched): NULL pointers, nxy < 1 or >= 2^40, Z < 1 or > 2^20, an unknown dtype, a scratch smaller than
+ * its query says, and what is listed per entry.  Only integer atomics: equal inputs give bit-identical results on every run.
+ *
+ * vg_slice_moments: mean_std[z] = (mean, population standard deviation) of vol[:, :, z], accumulated in fp64 as sums of (x - vol[0][0][z])
+ *   and of its square -- the pivot keeps E[d^2] - E[d]^2 free of cancellation and makes a constant slice give exactly 0 -- per workgroup
+ *   into the caller's scratch (vg_slice_moments_scratch_bytes(nxy, Z) bytes, 16-byte aligned), summed in a fixed order by a second
+ *   kernel and rounded once to fp32.
+ * vg_zscore_slices: out = s > 0 ? (x - m) / s : x - m in fp32 with (m, s) = mean_std[z]; ADDS the number of non-finite values written to
+ *   *nonfinite (one integer atomic per workgroup; zeroed by the caller).
+ * vg_order_stats: out[r] = sorted(x)[ranks[r]] for r < R (exact; -0.0 sorts before +0.0), x fp32 [n] of finite values (a NaN is ordered
+ *   by its bit pattern: beyond the infinity of its sign).  ranks is a HOST array; 1 <= R <= VG_PP_MAX_RANKS, 1 <= n < 2^31,
+ *   0 <= ranks[r] < n, duplicates allowed.  A most-significant-digit radix select, 8 bits per pass, on the order-preserving key of the
+ *   float's bits: per pass a histogram kernel over the whole array and a one-workgroup kernel that picks the bin; 9 launches whatever the
+ *   data, no host read-back.  scratch: vg_order_stats_scratch_bytes(n, R) bytes, 16-byte aligned, contents irrelevant on entry.
+ * vg_clip_rescale: stats4 = the order statistics (a[i], a[i+1], a[j], a[j+1]) on the device; the limits are formed as
+ *   scipy.stats.scoreatpercentile does, in fp64 with every operation rounded, lp = a[i] * (1 - f_lo) + a[i+1] * f_lo (up likewise from
+ *   f_hi; 0 <= f <= 1), rounded once to fp32 and written to limits2.  c = z < lp ? lp : z > up ? up : z, and
+ *   out = rescale ? ((c - lp) / (up - lp) - 0.5) / 0.5 : c in fp32, each operation rounded (rescale is 0 or 1).  out may be z itself.
+ * --------------------------------------------------------------------------------------------- */
+#define VG_PP_U8 0
+#define VG_PP_U16 1
+#define VG_PP_F32 2
+#define VG_PP_MAX_RANKS 4
+int64_t vg_slice_moments_scratch_bytes(int64_t nxy, int Z);
+int vg_slice_moments(const void* vol, int dtype, int64_t nxy, int Z, float* mean_std, void* scratch, int64_t scratch_bytes,
+                     vg_stream_t stream);
+int vg_zscore_slices(const void* vol, int dtype, int64_t nxy, int Z, const float* mean_std, float* out, uint32_t* nonfinite,
+                     vg_stream_t stream);
+int64_t vg_order_stats_scratch_bytes(int64_t n, int R);
+int vg_order_stats(const float* x, int64_t n, const int64_t* ranks_host, int R, float* out, void* scratch, int64_t scratch_bytes,
+                   vg_stream_t stream);
+int vg_clip_rescale(const float* z, int64_t n, const float* stats4, double f_lo, double f_hi, int rescale, float* limits2, float* out,
+                    vg_stream_t stream);
+
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */
 int vg_memset_zero(void* p, int64_t nbytes, vg_stream_t stream);

@@ -134,6 +134,12 @@ _SIGS = {
     'vg_divide_crop': ([c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p], c_int),
     'vg_window_gather': ([c_void_p, c_int, c_int, c_int, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p], c_int),
     'vg_window_scatter': ([c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 3, c_int),
+    'vg_slice_moments_scratch_bytes': ([c_i64, c_int], c_i64),
+    'vg_slice_moments': ([c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_i64, c_void_p], c_int),
+    'vg_zscore_slices': ([c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_order_stats_scratch_bytes': ([c_i64, c_int], c_i64),
+    'vg_order_stats': ([c_void_p, c_i64, C.POINTER(c_i64), c_int, c_void_p, c_void_p, c_i64, c_void_p], c_int),
+    'vg_clip_rescale': ([c_void_p, c_i64, c_void_p, C.c_double, C.c_double, c_int, c_void_p, c_void_p, c_void_p], c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

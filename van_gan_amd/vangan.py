@@ -1100,6 +1100,14 @@ class VanGan:
         self._join_updates()
         return _st(self, gen, img, tuple(subvol_size) if subvol_size is not None else self.dims, **kw)
 
+    def segment_volume(self, gen: str, raw, subvol_size=None, *, preprocess='rsom', lower_thresh: float = 0.05, upper_thresh: float = 99.95,
+                       check: bool = True, **stitch_kw):
+        """Raw volume -> segmentation on the device: the reference's recipe for new images (main.py:255-270), prepare_imaging
+        (van_gan_amd/preprocess.py) followed by stitch_subvolumes with the remaining keywords."""
+        from .preprocess import prepare_imaging
+        img = prepare_imaging(raw, preprocess=preprocess, lower_thresh=lower_thresh, upper_thresh=upper_thresh, check=check, device=self.device)
+        return self.stitch_subvolumes(gen, img, subvol_size, **stitch_kw)
+
     # ------------------------------------------------------------------------------------------------
     def save_checkpoint(self, epoch: int):
         """vangan.py:247-250 (own format: the TF tensor-bundle format is not readable without TF).  The replicas hold identical
