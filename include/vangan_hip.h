@@ -627,6 +627,35 @@ int vg_order_stats(const float* x, int64_t n, const int64_t* ranks_host, int R, 
 int vg_clip_rescale(const float* z, int64_t n, const float* stats4, double f_lo, double f_hi, int rescale, float* limits2, float* out,
                     vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Volume resize (resize_volume, utils.py:224-255: cv2.resize(..., INTER_LANCZOS4) slice by slice), restated; van_gan_amd/preprocess.py
+ * (lanczos4_table, resize_volume), csrc/vg_resample.hip, DESIGN.md section 3.13.  fp32, the same code in both storage builds.
+ * TP, unverifiable here: the filter below restates OpenCV's float32 single-channel Lanczos-4 resize from its published source; OpenCV
+ * itself was never run against this code.
+ *
+ * The filter of one axis, source length L -> target length T, built on the HOST (van_gan_amd.preprocess.lanczos4_table):
+ *   scale = 1.0 / (T / L) in fp64; for dx = 0 .. T-1: fx = (float)((dx + 0.5) * scale - 0.5), sx = floor(fx), t = fx - (float)sx in fp32;
+ *   first[dx] = sx - 3 (unclamped: -3 .. L + 3 occur); the 8 taps read source indices clamp(first[dx] + k, 0, L - 1), k = 0 .. 7 (OpenCV
+ *   replicates the edge).  Coefficients of a phase t: t < FLT_EPSILON gives the unit tap at k = 3; else, in fp64, y_k = -(t + 3 - k) * pi / 4,
+ *   c_k = (float)((-1)^k sin(y_k) / y_k^2) -- formed, as OpenCV forms it, from sin y_0, cos y_0 and the eighth-turn table
+ *   {(1,0), (-s,-s), (0,1), (s,-s), (-1,0), (s,s), (0,-1), (-s,s)}, s = sqrt(1/2) -- S = c_0 + ... + c_7 in fp32 in that order and
+ *   w_k = c_k * (float)(1 / S) in fp32: sinc(u) sinc(u / 4) at u = t + 3 - k, normalised to sum 1.
+ * A volume [X][Y][Z] is resized by up to three passes with fp32 intermediates in the order Y, X, Z (OpenCV's 2-D resize runs columns, then
+ * rows; the reference resizes every z-slice, then every x-slab); an axis whose lengths are equal is skipped by the host.
+ *
+ * vg_resample_axis: one pass.  The volume is viewed as [outer][L][inner] -> [outer][T][inner]:
+ *   out[o][j][i] = sum_k w8[j][k] * x[o][clamp(first[j] + k, 0, L - 1)][i],  acc = w8[j][0] * x_0, then fmaf in tap order (fp32).
+ *   The passes of [X][Y][Z] -> [T0][T1][T2] are (outer, L, inner) = (X, Y, Z), (1, X, T1 * Z), (T0 * T1, Z, 1).  first: int32 [T] and w8:
+ *   fp32 [T][8] on the device; the clamp is applied by the kernel, so no table content can make a read leave its row.  inner >= 2 runs a
+ *   kernel whose lanes take neighbouring i (16-byte accesses when inner % 4 == 0 and x, out are 16-byte aligned, else 4-byte); inner == 1
+ *   stages whole rows in LDS (rows of more than 1023 floats are read from global memory directly).  Only enqueues, allocates nothing, keeps no
+ *   state, no atomics: equal inputs give equal bits.  A tap of weight 0 contributes +-0, so an identity table copies every value bit for bit
+ *   except that a -0.0 may come out as +0.0.  VG_EINVAL (nothing launched): a NULL pointer; outer, inner, L or T < 1; L or T > 2^20;
+ *   outer * max(L, T) * inner >= 2^40; out == x; a pointer that is not 4-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+int vg_resample_axis(const float* x, int64_t outer, int L, int64_t inner, int T, const int32_t* first, const float* w8, float* out,
+                     vg_stream_t stream);
+
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */
 int vg_memset_zero(void* p, int64_t nbytes, vg_stream_t stream);

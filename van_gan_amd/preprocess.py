@@ -1,8 +1,9 @@
 """Raw-volume preprocessing on MI355X: the imaging-domain recipe the reference runs before run_mapping (main.py:255-270) --
 preprocess_rsom_images (main.py:127-150: z-score every z-slice, clip to two percentiles of the whole volume with
 scipy.stats.scoreatpercentile) followed by process_tiff's min_max_norm and (x - 0.5) / 0.5 and its NaN check (preprocessing.py:179-215)
--- without the TIFF I/O, the resize and the label-domain branch.  The arithmetic runs in csrc/vg_preproc.hip
-(include/vangan_hip.h "Raw-volume preprocessing"); this module owns buffers, ranks and checks.
+-- and, on request, process_tiff's resize_volume between the two (utils.py:224-255: Lanczos-4) -- without the TIFF I/O and the label-domain
+branch.  The arithmetic runs in csrc/vg_preproc.hip and csrc/vg_resample.hip (include/vangan_hip.h "Raw-volume
+preprocessing" and "Volume resize", DESIGN.md sections 3.12 and 3.13); this module owns buffers, ranks, filter tables and checks.
 
 A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost -- process_tiff's layout after its transpose -- as uint8, uint16 or float32, a numpy
 array or a torch tensor, on the host or on the device.  torch has no uint16 arithmetic, so a 16-bit stack travels as the int16 tensor of
@@ -10,7 +11,9 @@ the same bytes and the kernels read it as what it is."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
+import operator
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -220,38 +223,186 @@ def preprocess_rsom_images(vol, lower_thresh: float = 0.05, upper_thresh: float 
     return z
 
 
+# ------------------------------------------------------------------------------------------------ Lanczos-4 volume resize
+# resize_volume (utils.py:224-255) resamples with cv2.resize(..., interpolation=cv2.INTER_LANCZOS4).  TP, unverifiable here: what follows
+# restates OpenCV's float32 single-channel Lanczos-4 resize (the index table of its resize, the coefficients of its interpolateLanczos4)
+# from its published source; OpenCV itself was never run against it.  The contract is in include/vangan_hip.h "Volume resize".
+LANCZOS_TAPS = 8
+MAX_AXIS = 1 << 20                         # vg_resample_axis serves L, T <= 2^20
+_FLT_EPSILON = float(np.finfo(np.float32).eps)
+_S45 = 0.70710678118654752440084436210485
+_CS = ((1.0, 0.0), (-_S45, -_S45), (0.0, 1.0), (_S45, -_S45), (-1.0, 0.0), (_S45, _S45), (0.0, -1.0), (-_S45, _S45))
+
+
+def lanczos4_weights(t) -> np.ndarray:
+    """The 8 float32 coefficients of the phase t in [0, 1) (a float32 value): the unit tap at k = 3 when t < FLT_EPSILON; else, in float64,
+    y_k = -(t + 3 - k) pi / 4 and c_k = float32((-1)^k sin(y_k) / y_k^2) with (-1)^k sin(y_k) = cs_k[0] sin(y_0) + cs_k[1] cos(y_0) (y_k is
+    y_0 advanced by k eighths of a turn), summed in float32 in tap order and scaled by float32(1 / sum): sinc(u) sinc(u / 4) at
+    u = t + 3 - k, normalised.  math.sin / math.cos: one libm whatever the numpy build."""
+    t = float(np.float32(t))
+    w = np.zeros(LANCZOS_TAPS, np.float32)
+    if t < _FLT_EPSILON:
+        w[3] = 1.0
+        return w
+    y0 = -(t + 3.0) * math.pi * 0.25
+    s0, c0 = math.sin(y0), math.cos(y0)
+    total = np.float32(0.0)
+    for k in range(LANCZOS_TAPS):
+        y = -(t + 3.0 - k) * math.pi * 0.25
+        w[k] = np.float32((_CS[k][0] * s0 + _CS[k][1] * c0) / (y * y))
+        total = np.float32(total + w[k])
+    return w * np.float32(np.float32(1.0) / total)
+
+
+@functools.lru_cache(maxsize=32)
+def _lanczos4_table(L: int, T: int):
+    scale = 1.0 / (T / L)
+    fx = ((np.arange(T, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    sx = np.floor(fx)
+    t = fx - sx                                                    # float32 - float32
+    w8 = np.empty((T, LANCZOS_TAPS), np.float32)
+    phases = {}
+    for j, tj in enumerate(t.tolist()):                            # the phases of a rational scale repeat: each is evaluated once
+        w = phases.get(tj)
+        if w is None:
+            w = phases[tj] = lanczos4_weights(tj)
+        w8[j] = w
+    first = sx.astype(np.int32) - np.int32(3)
+    first.setflags(write=False), w8.setflags(write=False)
+    return first, w8
+
+
+def lanczos4_table(L: int, T: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(first int32 [T], w8 float32 [T, 8]) of one axis resized from L to T samples, on the host (read-only arrays): output dx reads the
+    source indices first[dx] + k, k = 0 .. 7, each clamped to [0, L - 1] by the kernel, with the weights w8[dx].  scale = 1 / (T / L) in
+    float64, fx = float32((dx + 0.5) scale - 0.5), sx = floor(fx), t = fx - float32(sx) in float32, first = sx - 3, w8[dx] =
+    lanczos4_weights(t)."""
+    L, T = operator.index(L), operator.index(T)
+    if not (1 <= L <= MAX_AXIS and 1 <= T <= MAX_AXIS):
+        raise ValueError('an axis is resized from 1 <= L <= 2^20 to 1 <= T <= 2^20 samples, got L = %d, T = %d' % (L, T))
+    return _lanczos4_table(L, T)
+
+
+def _target3(target_size) -> Tuple[int, int, int]:
+    """Three integers >= 1 (a trailing 1 is tolerated, as in a volume's shape)."""
+    try:
+        tgt = tuple(operator.index(s) for s in target_size)
+    except TypeError:
+        raise ValueError('target_size is three integers, got %r' % (target_size,)) from None
+    if len(tgt) == 4 and tgt[3] == 1:
+        tgt = tgt[:3]
+    if len(tgt) != 3 or min(tgt) < 1 or max(tgt) > MAX_AXIS:
+        raise ValueError('target_size is three integers in [1, 2^20], got %r' % (target_size,))
+    return tgt
+
+
+def _upload_table(first, w8, T: int, dev: torch.device) -> torch.Tensor:
+    """first [T] and w8 [T, 8] as one int32 device buffer of 9 T words (one upload of 36 T bytes): first, then the bits of w8."""
+    first, w8 = np.ascontiguousarray(first, np.int32), np.ascontiguousarray(w8, np.float32)
+    if first.shape != (T,) or w8.shape != (T, LANCZOS_TAPS):
+        raise ValueError('a table is (first int32 [T], w8 float32 [T, 8])')
+    return torch.from_numpy(np.concatenate([first, w8.ravel().view(np.int32)])).to(dev)
+
+
+@functools.lru_cache(maxsize=32)
+def _device_table(L: int, T: int, dev: torch.device) -> torch.Tensor:
+    """The uploaded lanczos4_table(L, T), kept per device: a later resize between the same lengths neither rebuilds nor uploads it, so the
+    call only enqueues.  Read-only on the device; at most 32 tables of 36 T bytes are held."""
+    first, w8 = lanczos4_table(L, T)
+    return _upload_table(first, w8, T, dev)
+
+
+def resample_axis(x: torch.Tensor, T: int, table=None) -> torch.Tensor:
+    """One pass of the resize: x fp32 [outer, L, inner] on the device -> [outer, T, inner], resampled along its middle axis with
+    lanczos4_table(L, T), or with table = (first int32 [T], w8 float32 [T, 8]) given as host arrays.  Enqueue-only; x is not modified."""
+    T = operator.index(T)
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise ValueError('x must be a contiguous fp32 device tensor [outer, L, inner]')
+    outer, L, inner = x.shape
+    with torch.cuda.device(x.device):
+        tab = _device_table(L, T, x.device) if table is None else _upload_table(table[0], table[1], T, x.device)
+        out = torch.empty(outer, T, inner, device=x.device)
+        _check(lib.vg_resample_axis(_p(x), outer, L, inner, T, _p(tab), _p(tab) + 4 * T, _p(out), stream()), 'vg_resample_axis')
+    return out
+
+
+def _resize_f32(x: torch.Tensor, tgt: Tuple[int, int, int]) -> torch.Tensor:
+    """x: fp32 [X,Y,Z] on the device, contiguous.  The passes Y, X, Z; an axis that already has its length is skipped."""
+    for axis in (1, 0, 2):
+        s = x.shape
+        if s[axis] != tgt[axis]:
+            outer, inner = math.prod(s[:axis]), math.prod(s[axis + 1:])
+            x = resample_axis(x.view(outer, s[axis], inner), tgt[axis]).view(s[:axis] + (tgt[axis],) + s[axis + 1:])
+    return x
+
+
+def _to_f32(v: RawVolume, counter_ptr: int) -> torch.Tensor:
+    """The conversion to fp32: the z-score kernel with a table of zeros computes x - 0 (and counts the non-finite values)."""
+    ms = torch.zeros(v.shape[2], 2, device=v.buf.device)
+    z = torch.empty(v.shape, device=v.buf.device)
+    _zscore_into(v, ms, z, counter_ptr)
+    return z
+
+
+def resize_volume(vol, target_size, device=None) -> torch.Tensor:
+    """resize_volume (utils.py:224-255) on the device: vol [X,Y,Z] (whatever as_raw_volume takes; uint8 / uint16 stacks are converted to
+    fp32 first) -> fp32 [T0,T1,T2], Lanczos-4 as cv2.resize(..., INTER_LANCZOS4) computes it on float32 (TP: restated, never run against
+    OpenCV).  The reference resizes every z-slice in 2-D (OpenCV: columns, then rows), then every x-slab; as 1-D passes with fp32
+    intermediates that is Y, then X, then Z, and Z alone when X and Y already match.  An axis whose length equals its target is skipped
+    (OpenCV <= 4.5 applies the exact unit tap there; newer versions differ from it by at most one ulp: the one known ambiguity).  The
+    reference works only for target_size[0] == target_size[1] -- its slice assignment needs that; here axis a simply goes to
+    target_size[a].  Enqueue-only; arguments are validated before the device is touched.  When no pass is needed the fp32 volume itself is
+    returned (for an fp32 device tensor: the same storage)."""
+    tgt = _target3(target_size)
+    v = as_raw_volume(vol, device)
+    dev = v.buf.device
+    with torch.cuda.device(dev):
+        x = v.buf.view(v.shape) if v.code == PP_F32 else _to_f32(v, _p(_state_block(dev)))
+        return _resize_f32(x, tgt)
+
+
+def _minmax_rescale(x: torch.Tensor, limits_ptr: int) -> None:
+    """min_max_norm and (x - 0.5) / 0.5 in place: vg_minmax finds the extremes, and the clip pass with (min, max) as its limits (fractions 0)
+    clips nothing and applies ((x - min) / (max - min) - 0.5) / 0.5; it also files (min, max) at limits_ptr."""
+    n = x.numel()
+    mm = torch.zeros(1, 4, device=x.device)
+    _check(lib.vg_minmax(_p(x), 1, n, _p(mm), stream()), 'vg_minmax')
+    stats = torch.stack((mm[0, 0], mm[0, 1], mm[0, 1], mm[0, 1]))
+    _check(lib.vg_clip_rescale(_p(x), n, _p(stats), 0.0, 0.0, 1, limits_ptr, _p(x), stream()), 'vg_clip_rescale')
+
+
 def prepare_imaging(raw, preprocess: Optional[str] = 'rsom', lower_thresh: float = 0.05, upper_thresh: float = 99.95, check: bool = True,
-                    device=None) -> torch.Tensor:
+                    device=None, target_size=None) -> torch.Tensor:
     """Raw imaging volume -> what stitch_subvolumes and DataPipeline take: fp32 [X,Y,Z,1] in [-1, 1] on the device.
     preprocess='rsom': z-score per z-slice, clip to the two percentiles, min-max, (x - 0.5) / 0.5 (main.py:127-150 and
     preprocessing.py:179-185).  preprocess=None: min-max and (x - 0.5) / 0.5 alone (process_tiff without a preprocess_fn).
     check=True reads one small block back and raises ValueError('NaN detected') when a non-finite value was met (preprocessing.py:191-215
     prints that and skips the file) and min_max_norm's ValueError when the two limits coincide.  check=False reads nothing back: the call
-    only enqueues, and the launches it makes do not depend on the data."""
+    only enqueues, and the launches it makes do not depend on the data.
+    target_size=(T0, T1, T2): process_tiff's resize=True (preprocessing.py:170-185) -- the preprocessed volume (clipped, not yet rescaled)
+    goes through resize_volume before min_max_norm, and the result is [T0,T1,T2,1].  Lanczos-4 overshoots, so the extremes are taken from
+    the resized volume by a min / max pass.  The non-finite count is that of the values before the resize.  None: no resize, today's
+    launches; a target equal to the volume's shape gives the same bits as None."""
     if preprocess not in ('rsom', None):
         raise ValueError("preprocess must be 'rsom' or None, got %r" % (preprocess,))
     percentile_rank(1, lower_thresh), percentile_rank(1, upper_thresh)
+    tgt = None if target_size is None else _target3(target_size)
     v = as_raw_volume(raw, device)
     dev = v.buf.device
-    n = v.numel
     with torch.cuda.device(dev):
         state = _state_block(dev)
-        ms = torch.empty(v.shape[2], 2, device=dev) if preprocess else torch.zeros(v.shape[2], 2, device=dev)
-        z = torch.empty(v.shape, device=dev)
         if preprocess:
+            ms = torch.empty(v.shape[2], 2, device=dev)
+            out = torch.empty(v.shape, device=dev)
             _moments_into(v, ms)
-            _zscore_into(v, ms, z, _p(state))
-            _clip_into(z, lower_thresh, upper_thresh, True, _p(state) + 8, z)
-            out = z
+            _zscore_into(v, ms, out, _p(state))
+            _clip_into(out, lower_thresh, upper_thresh, tgt is None, _p(state) + 8, out)
         else:
-            _zscore_into(v, ms, z, _p(state))            # mean 0, std 0: x - 0, the conversion to fp32 (and the non-finite count)
-            mm = torch.zeros(1, 4, device=dev)
-            _check(lib.vg_minmax(_p(z), 1, n, _p(mm), stream()), 'vg_minmax')
-            # the clip pass with (min, max) as its limits (fractions 0) clips nothing and applies ((x - min) / (max - min) - 0.5) / 0.5 in
-            # place; it also files (min, max) beside the counter
-            stats = torch.stack((mm[0, 0], mm[0, 1], mm[0, 1], mm[0, 1]))
-            _check(lib.vg_clip_rescale(_p(z), n, _p(stats), 0.0, 0.0, 1, _p(state) + 8, _p(z), stream()), 'vg_clip_rescale')
-            out = z
+            out = _to_f32(v, _p(state))
+        if tgt is not None:
+            out = _resize_f32(out, tgt)                 # `out` itself when no axis changes: ours, so the rescale below may run in place
+        if tgt is not None or not preprocess:
+            _minmax_rescale(out, _p(state) + 8)
         if check:
             host = state.cpu()
             if int(host[0]) != 0:
@@ -260,4 +411,3 @@ def prepare_imaging(raw, preprocess: Optional[str] = 'rsom', lower_thresh: float
             if float(lims[0]) == float(lims[1]):
                 raise ValueError(MINMAX_ERROR)
     return out[..., None]
-
