@@ -20,9 +20,6 @@ PROBES = {
     'train_lanes_side': dict(VG_LANES='1', VG_SIDE_STREAM='1', VG_OPT_STREAM='0'),
     'train_lanes_opt': dict(VG_LANES='1', VG_SIDE_STREAM='0', VG_OPT_STREAM='1'),
     'train_side_opt': dict(VG_LANES='0', VG_SIDE_STREAM='1', VG_OPT_STREAM='1'),
-    'train_full_nolazy': dict(VG_LAZY_AR='0'),
-    'train_full_noforkshort': dict(VG_FORK_SHORT='0'),
-    'train_full_nojoin0': dict(VG_NOJOIN='0'),
     'train_full': {},
 }
 

@@ -18,7 +18,7 @@ from . import ops
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, Arena, ConvLayer, Src
 
 GEN_F = [16, 32, 64, 128, 256]
-_STEM_AUX = os.environ.get('VG_STEM_AUX', '1') != '0'      # the stem shortcut's kernel gradient in closed form from the statistics pass (backward_iter)
+_STEM_AUX = os.environ.get('VG_STEM_AUX', '1') != '0'      # the stem shortcut's kernel gradient in closed form from the statistics pass (ResUNet.backward)
 # The stem's shortcut is never materialised: Conv3D(16, 1x1x1)(x) -> InstanceNorm of the single-channel volume is an affine function of x per
 # (sample, channel) -- vg_stem_short_fwd gives scale / shift from the volume's mean and variance, stem.cb's epilogue adds scale * x + shift
 # (vg_conv_desc::res_c1).  No 1 -> 16 launch, no 16-channel tensor written and read back (64 B per voxel and application), and the branch
@@ -241,16 +241,6 @@ class Norm:
         return st
 
 
-def run_to_end(it):
-    """Exhaust a generator and return its value (the *_iter methods of the networks are generators so that the engine can enqueue
-    two of them alternately; called directly they run in one go)."""
-    try:
-        while True:
-            next(it)
-    except StopIteration as e:
-        return e.value
-
-
 def pair_ctx(ar: Arena, ctx: dict, x_full: torch.Tensor, ys, lv0) -> dict:
     """The backward context of BOTH applications of a generator whose forward passes ran in the arena's paired mode
     (Arena.pair_begin): ctx is the first application's context; every stored tensor is replaced by the 2N-sample tensor it is the
@@ -401,22 +391,19 @@ class ResUNet:
         lay.dgrad(dphi, N, low.grad, accumulate=True)
         ar.release(mk, defer=True)
 
-    def _block_fwd(self, ar: Arena, name: str, N: int, src_raw: Src, nrm_inputs, out_dims, co, ctx, save: bool = True, n1=None,
-                   out_jobs=None, out: Optional[Act] = None):
+    def _block_fwd(self, ar: Arena, name: str, N: int, src_raw: Src, n1: dict, out_dims, co, ctx, save: bool = True, out_jobs=None,
+                   out: Optional[Act] = None):
         """residual_block (resunet_model.py:103-143): out = conv2(relu(IN(conv1(relu(IN(x)))))) + IN(short(x)).
         save=False (inference): the block output is allocated first and everything else the block allocates (r, the
         shortcut, the InstanceNorm scale/shift vectors) is handed back to the arena once the block's kernels are queued.
-        n1 / out_jobs (ops.FIN_TAIL): the state of the block's first norm, already filled by the launches that produced its input, and
-        the consumer entries (Norm.job) of the norms that read the block's OUTPUT -- finalised by the block's last convolution."""
+        n1 / out_jobs: the state of the block's first norm, already filled by the launches that produced its input, and the consumer
+        entries (Norm.job) of the norms that read the block's OUTPUT -- finalised by the block's last convolution."""
         L, Nn = self.L, self.Nn
         mk = None
         if not save:
             if out is None:
                 out = Act(ar, N, out_dims, co, dtype=self.dtype)
             mk = ar.mark()
-        tail = n1 is not None
-        if not tail:
-            n1 = Nn[name + '.cb1'].finalize(ar, *nrm_inputs)
         s1 = Src(src_raw.x0, (N,) + tuple(L[name + '.cb1'].in_dims), src_raw.c0, src_raw.x1, src_raw.c1, src_raw.shift0,
                  scale=n1['scale'], shift=n1['shift'], act=ACT_RELU)
         r = Act(ar, N, out_dims, co, dtype=self.dtype)
@@ -425,23 +412,18 @@ class ResUNet:
         # lane's side stream (idle in the forward pass) it leaves the dependent chain, which on the deep levels is all latency
         # (28.45 -> 28.30 ms per step, inference 49.6 -> 48.4 ms per volume).  The same for the shortcut's IN backward on an
         # auxiliary stream per lane was measured slower (29.3 ms): the backward already runs four streams.
-        if tail:
-            ns, n2 = Nn[name + '.short'].state(ar, N), Nn[name + '.cb2'].state(ar, N)
-            f_s = ops.fin_desc(ar, sc.count, [Nn[name + '.short'].job(ns)])
-            f_1 = ops.fin_desc(ar, r.count, [Nn[name + '.cb2'].job(n2)])
+        ns, n2 = Nn[name + '.short'].state(ar, N), Nn[name + '.cb2'].state(ar, N)
+        f_s = ops.fin_desc(ar, sc.count, [Nn[name + '.short'].job(ns)])
+        f_1 = ops.fin_desc(ar, r.count, [Nn[name + '.cb2'].job(n2)])
         fork = ops.fork_side()
         with fork:
-            L[name + '.short'].forward(src_raw, sc.data, sums=sc.sums, fin=f_s if tail else None)
-            if not tail:
-                ns = Nn[name + '.short'].finalize(ar, sc)
-        L[name + '.cb1'].forward(s1, r.data, sums=r.sums, fin=f_1 if tail else None)
-        if not tail:
-            n2 = Nn[name + '.cb2'].finalize(ar, r)
+            L[name + '.short'].forward(src_raw, sc.data, sums=sc.sums, fin=f_s)
+        L[name + '.cb1'].forward(s1, r.data, sums=r.sums, fin=f_1)
         fork.join()
         s2 = Src(r.data, (N,) + tuple(out_dims), co, scale=n2['scale'], shift=n2['shift'], act=ACT_RELU)
         if out is None:
             out = Act(ar, N, out_dims, co, dtype=self.dtype)
-        f_o = ops.fin_desc(ar, out.count, out_jobs) if (tail and out_jobs) else None
+        f_o = ops.fin_desc(ar, out.count, out_jobs) if out_jobs else None
         L[name + '.cb2'].forward(s2, out.data, sums=out.sums, res=sc.data, res_scale=ns['scale'], res_shift=ns['shift'], fin=f_o)
         if save:
             ctx[name] = dict(n1=n1, s1=s1, r=r, sc=sc, ns=ns, n2=n2, s2=s2, out=out, src_raw=src_raw)
@@ -452,44 +434,36 @@ class ResUNet:
     def forward(self, ar: Arena, x: torch.Tensor, y: torch.Tensor, save: bool = True) -> dict:
         """x: fp32 [N,D,H,W,1]; y: fp32 [N,D,H,W,1] output buffer (tanh).  Returns the context for backward
         (save=True) or a stub (save=False: forward-only, block temporaries are recycled -- sliding-window inference)."""
-        return run_to_end(self.forward_iter(ar, x, y, save))
-
-    def forward_iter(self, ar: Arena, x: torch.Tensor, y: torch.Tensor, save: bool = True):
-        """forward() as a generator that yields between blocks: the host enqueues ~60 launches per application, and two
-        applications on two stream lanes enqueued one after the other leave the second lane idle for the first one's whole enqueue
-        time; the engine steps two of these alternately (vangan.interleave)."""
         N = x.shape[0]
         f, lv, L, Nn = GEN_F, self.lv, self.L, self.Nn
         ctx = {'N': N, 'x': x, 'y': y}
-        # ops.FIN_TAIL: every InstanceNorm's scale / shift / mean / rstd is written by the last workgroup of the launch that produces
-        # the norm's input (vg_fin_desc) -- 30 vg_in_finalize launches per application leave the lane's dependent chain.  A block's
+        # Every InstanceNorm's scale / shift / mean / rstd is written by the last workgroup of the launch that produces the norm's
+        # input (vg_fin_desc) -- 30 vg_in_finalize launches per application leave the lane's dependent chain.  A block's
         # FIRST norm reads the previous block's output (a decoder block's: [upsampled low-resolution output; encoder skip], two
         # producers, two channel ranges of one array), so those states exist before the first launch.
-        tail = ops.FIN_TAIL
         gate = self.attention_gate
         pre, jobs = {}, {}
-        if tail:
-            pre['stem.cb'], pre['stem.short'] = Nn['stem.cb'].state(ar, N), Nn['stem.short'].state(ar, N)
-            # (attention gate: a decoder block's first norm reads [upsampled low output; GATED skip]; its state is finalised by one
-            #  vg_in_finalize launch behind the gate, from low.sums and the gate launch's sums -- no state here, no producer entry below)
-            for b in ['enc%d' % e for e in range(1, 5)] + ([] if gate else ['dec%d' % d for d in (3, 2, 1, 0)]):
-                pre[b] = Nn[b + '.cb1'].state(ar, N)
-            pre['bridge.cb1'], pre['bridge.cb2'] = Nn['bridge.cb1'].state(ar, N), Nn['bridge.cb2'].state(ar, N)
-            # consumers of every block output: skips[d] (stem, enc1..enc3) feeds enc(d+1).cb1 and, behind the f[d+1] upsampled
-            # channels, dec(d).cb1; enc4 feeds the bridge; bridge / dec outputs feed the next decoder block's low half
-            dec_job = (lambda d, c_off=0: []) if gate else (lambda d, c_off=0: [Nn['dec%d.cb1' % d].job(pre['dec%d' % d], c_off)])
-            jobs['stem'] = [Nn['enc1.cb1'].job(pre['enc1'])] + dec_job(0, f[1])
-            for e in range(1, 4):
-                jobs['enc%d' % e] = [Nn['enc%d.cb1' % (e + 1)].job(pre['enc%d' % (e + 1)])] + dec_job(e, f[e + 1])
-            jobs['enc4'] = [Nn['bridge.cb1'].job(pre['bridge.cb1'])]
-            jobs['bridge.cb1'] = [Nn['bridge.cb2'].job(pre['bridge.cb2'])]
-            jobs['bridge.cb2'] = dec_job(3)
-            for d in (3, 2, 1):
-                jobs['dec%d' % d] = dec_job(d - 1)
-            jobs['dec0'] = None
+        pre['stem.cb'], pre['stem.short'] = Nn['stem.cb'].state(ar, N), Nn['stem.short'].state(ar, N)
+        # (attention gate: a decoder block's first norm reads [upsampled low output; GATED skip]; its state is finalised by one
+        #  vg_in_finalize launch behind the gate, from low.sums and the gate launch's sums -- no state here, no producer entry below)
+        for b in ['enc%d' % e for e in range(1, 5)] + ([] if gate else ['dec%d' % d for d in (3, 2, 1, 0)]):
+            pre[b] = Nn[b + '.cb1'].state(ar, N)
+        pre['bridge.cb1'], pre['bridge.cb2'] = Nn['bridge.cb1'].state(ar, N), Nn['bridge.cb2'].state(ar, N)
+        # consumers of every block output: skips[d] (stem, enc1..enc3) feeds enc(d+1).cb1 and, behind the f[d+1] upsampled
+        # channels, dec(d).cb1; enc4 feeds the bridge; bridge / dec outputs feed the next decoder block's low half
+        dec_job = (lambda d, c_off=0: []) if gate else (lambda d, c_off=0: [Nn['dec%d.cb1' % d].job(pre['dec%d' % d], c_off)])
+        jobs['stem'] = [Nn['enc1.cb1'].job(pre['enc1'])] + dec_job(0, f[1])
+        for e in range(1, 4):
+            jobs['enc%d' % e] = [Nn['enc%d.cb1' % (e + 1)].job(pre['enc%d' % (e + 1)])] + dec_job(e, f[e + 1])
+        jobs['enc4'] = [Nn['bridge.cb1'].job(pre['bridge.cb1'])]
+        jobs['bridge.cb1'] = [Nn['bridge.cb2'].job(pre['bridge.cb2'])]
+        jobs['bridge.cb2'] = dec_job(3)
+        for d in (3, 2, 1):
+            jobs['dec%d' % d] = dec_job(d - 1)
+        jobs['dec0'] = None
         sx = Src(x, (N,) + lv[0], 1, f32=True)
         c1 = Act(ar, N, lv[0], f[0], dtype=self.dtype)
-        L['stem.conv1'].forward(sx, c1.data, sums=c1.sums, fin=ops.fin_desc(ar, c1.count, [Nn['stem.cb'].job(pre['stem.cb'])]) if tail else None)
+        L['stem.conv1'].forward(sx, c1.data, sums=c1.sums, fin=ops.fin_desc(ar, c1.count, [Nn['stem.cb'].job(pre['stem.cb'])]))
         fused = _STEM_FUSED and _STEM_AUX
         if fused:
             sc = None
@@ -498,39 +472,36 @@ class ResUNet:
                                round16=self.dtype != torch.float32)
         else:
             sc = Act(ar, N, lv[0], f[0], dtype=self.dtype)
-            L['stem.short'].forward(sx, sc.data, sums=sc.sums, fin=ops.fin_desc(ar, sc.count, [Nn['stem.short'].job(pre['stem.short'])]) if tail else None)
-            ns = pre['stem.short'] if tail else Nn['stem.short'].finalize(ar, sc)
-        n1 = pre['stem.cb'] if tail else Nn['stem.cb'].finalize(ar, c1)
+            L['stem.short'].forward(sx, sc.data, sums=sc.sums, fin=ops.fin_desc(ar, sc.count, [Nn['stem.short'].job(pre['stem.short'])]))
+            ns = pre['stem.short']
+        n1 = pre['stem.cb']
         s1 = Src(c1.data, (N,) + lv[0], f[0], scale=n1['scale'], shift=n1['shift'], act=ACT_RELU)
         h = Act(ar, N, lv[0], f[0], dtype=self.dtype)
         L['stem.cb'].forward(s1, h.data, sums=h.sums, res=x if fused else sc.data, res_scale=ns['scale'], res_shift=ns['shift'],
-                             fin=ops.fin_desc(ar, h.count, jobs['stem']) if tail else None, res_c1=fused)
+                             fin=ops.fin_desc(ar, h.count, jobs['stem']), res_c1=fused)
         ctx['stem'] = dict(sx=sx, c1=c1, sc=sc, ns=ns, n1=n1, s1=s1, out=h)
-        yield
         skips = [h]
         for e in range(1, 5):
             raw = Src(h.data, (N,) + lv[e - 1], f[e - 1])
             b = 'enc%d' % e
-            h = self._block_fwd(ar, b, N, raw, (h,), lv[e], f[e], ctx, save, n1=pre.get(b), out_jobs=jobs.get(b))
+            h = self._block_fwd(ar, b, N, raw, pre[b], lv[e], f[e], ctx, save, out_jobs=jobs[b])
             if save:
                 ctx['enc%d' % e]['inp'] = (skips[-1],)
             skips.append(h)
-            yield
-        nb1 = pre['bridge.cb1'] if tail else Nn['bridge.cb1'].finalize(ar, h)
+        nb1 = pre['bridge.cb1']
         sb1 = Src(h.data, (N,) + lv[4], f[4], scale=nb1['scale'], shift=nb1['shift'], act=ACT_RELU)
         b1 = Act(ar, N, lv[4], f[4], dtype=self.dtype)
-        L['bridge.cb1'].forward(sb1, b1.data, sums=b1.sums, fin=ops.fin_desc(ar, b1.count, jobs['bridge.cb1']) if tail else None)
-        nb2 = pre['bridge.cb2'] if tail else Nn['bridge.cb2'].finalize(ar, b1)
+        L['bridge.cb1'].forward(sb1, b1.data, sums=b1.sums, fin=ops.fin_desc(ar, b1.count, jobs['bridge.cb1']))
+        nb2 = pre['bridge.cb2']
         sb2 = Src(b1.data, (N,) + lv[4], f[4], scale=nb2['scale'], shift=nb2['shift'], act=ACT_RELU)
         b2 = Act(ar, N, lv[4], f[4], dtype=self.dtype)
-        L['bridge.cb2'].forward(sb2, b2.data, sums=b2.sums, fin=ops.fin_desc(ar, b2.count, jobs['bridge.cb2']) if (tail and jobs['bridge.cb2']) else None)
+        L['bridge.cb2'].forward(sb2, b2.data, sums=b2.sums, fin=ops.fin_desc(ar, b2.count, jobs['bridge.cb2']) if jobs['bridge.cb2'] else None)
         ctx['bridge'] = dict(inp=h, nb1=nb1, sb1=sb1, b1=b1, nb2=nb2, sb2=sb2, b2=b2)
         h = b2
         for d in (3, 2, 1, 0):
             skip = skips[d]
             raw = Src(h.data, (N,) + lv[d], h.C, skip.data, skip.C, shift0=1)       # virtual upsample + concat
             low = h
-            yield
             b = 'dec%d' % d
             if self.attention_gate:
                 out_pre = mkg = None
@@ -539,15 +510,15 @@ class ResUNet:
                     mkg = ar.mark()
                 gs, gctx = self._gate_fwd(ar, d, N, low, skip)
                 raw = Src(low.data, (N,) + lv[d], low.C, gs.data, gs.C, shift0=1)
-                n1 = Nn[b + '.cb1'].finalize(ar, low, gs) if tail else None
-                h = self._block_fwd(ar, b, N, raw, (low, gs), lv[d], f[d], ctx, save, n1=n1, out_jobs=jobs.get(b), out=out_pre)
+                n1 = Nn[b + '.cb1'].finalize(ar, low, gs)
+                h = self._block_fwd(ar, b, N, raw, n1, lv[d], f[d], ctx, save, out_jobs=jobs[b], out=out_pre)
                 if save:
                     ctx[b]['inp'] = (low, gs)
                     ctx[b]['gate'] = gctx
                 else:
                     ar.release(mkg)
                 continue
-            h = self._block_fwd(ar, b, N, raw, (low, skip), lv[d], f[d], ctx, save, n1=pre.get(b), out_jobs=jobs.get(b))
+            h = self._block_fwd(ar, b, N, raw, pre[b], lv[d], f[d], ctx, save, out_jobs=jobs[b])
             if save:
                 ctx['dec%d' % d]['inp'] = (low, skip)
         so = Src(h.data, (N,) + lv[0], f[0])
@@ -626,15 +597,12 @@ class ResUNet:
                 short.dgrad_concat(d_sc, N, dcat, low.C, low.grad, skip.grad, acc_low=a_low, acc_skip=a_skip)
         ar.release(mk, defer=True)
 
-    def backward(self, ar: Arena, ctx: dict, gy: torch.Tensor, inline_from: int = -1):
-        run_to_end(self.backward_iter(ar, ctx, gy, inline_from))
-
     def grad_suffix_offset(self, first_param: str = 'enc4.cb1.in.gamma') -> int:
         """Offset of `first_param` in the flat parameter / gradient buffer: everything from there to the end (enc4, bridge, decoder,
         output head: 34 of the 38 MB) is complete once the backward sweep has finished block enc4."""
         return self.store.offsets[first_param][0]
 
-    def backward_iter(self, ar: Arena, ctx: dict, gy: torch.Tensor, inline_from: int = -1, on_suffix_done=None):
+    def backward(self, ar: Arena, ctx: dict, gy: torch.Tensor, inline_from: int = -1, on_suffix_done=None):
         """gy: fp32 [N,D,H,W,1] gradient w.r.t. the tanh output.  Adds parameter gradients into store.g.
         inline_from (the LAST sweep of a lane): the weight gradients of encoder blocks <= inline_from and of the stem are launched on
         the lane itself instead of its side stream -- at the end of a step the side stream is a couple of milliseconds behind the
@@ -664,7 +632,6 @@ class ResUNet:
             self._block_bwd(ar, 'dec%d' % d, ctx['dec%d' % d], N)
             if self.attention_gate:
                 self._gate_bwd(ar, d, ctx['dec%d' % d], N)
-            yield
         # bridge
         b = ctx['bridge']
         mk = ar.mark()
@@ -678,11 +645,9 @@ class ResUNet:
         self._dgrad_norm_bwd(ar, cb1, d_b1, N, dp, b['sb1'], b['nb1'], Nn['bridge.cb1'], b['inp'].grad, ACT_RELU, accumulate=not b['inp'].first_write())
         ar.release(mk, defer=True)
         for e in (4, 3, 2, 1):
-            yield
             self._block_bwd(ar, 'enc%d' % e, ctx['enc%d' % e], N, inline=e <= inline_from)   # the sweep's last weight gradients on the lane itself
             if e == 4 and on_suffix_done is not None:
                 on_suffix_done()                 # gradients of enc4 ... output head are complete (data parallel: reduce them now)
-        yield
         inl = inline_from >= 0
         # stem
         s = ctx['stem']
@@ -851,11 +816,6 @@ class ResNetGenerator:
 
     DROP_RATES = {'c7': 0.5, 'down0': 0.2, 'down1': 0.2, 'down2': 0.2}      # generator.py:44, building_blocks.py downsample()
     DROP_CH = {'c7': RESNET_F, 'down0': 2 * RESNET_F, 'down1': 4 * RESNET_F, 'down2': 8 * RESNET_F}
-
-    def forward_iter(self, ar: Arena, x: torch.Tensor, y: torch.Tensor, drop: Optional[dict] = None):
-        """The engine's resumable-enqueue protocol (ResUNet.forward_iter): this network is enqueued in one piece."""
-        return self.forward(ar, x, y, drop() if callable(drop) else drop)
-        yield
 
     def _in_bwd(self, ar: Arena, g, g_padded: bool, raw: 'Act', st: dict, norm: 'Norm', act: int):
         """(InstanceNorm -> act -> dropout) backward of the tensor raw.data given the gradient g of its transformed value (on the
@@ -1049,16 +1009,15 @@ class PatchGAN:
                     acts.append(h)
             ctx.update(acts=acts, srcs=srcs, sts=sts)
             return ctx
-        tail = ops.FIN_TAIL
         h = Act(ar, N, lv[1], 64, dtype=self.dtype)
-        # (ops.FIN_TAIL: the norm behind a convolution -- with that layer's channel-dropout multipliers folded in -- is finalised by the
+        # (the norm behind a convolution -- with that layer's channel-dropout multipliers folded in -- is finalised by the
         # convolution's own launch: four vg_in_finalize launches per application leave the chain)
-        nxt = Nn['conv0'].state(ar, N, mult=None) if tail else None
-        L['conv0'].forward(src, h.data, sums=h.sums, fin=ops.fin_desc(ar, h.count, [Nn['conv0'].job(nxt)]) if tail else None)
+        nxt = Nn['conv0'].state(ar, N, mult=None)
+        L['conv0'].forward(src, h.data, sums=h.sums, fin=ops.fin_desc(ar, h.count, [Nn['conv0'].job(nxt)]))
         acts.append(h)
         prev_drop = None
-        for i, k in enumerate(['down0', 'down1', 'down2', 'out']):
-            st = nxt if tail else Nn[self.NAMES[i]].finalize(ar, h, mult=prev_drop)
+        for k in ['down0', 'down1', 'down2', 'out']:
+            st = nxt
             sts.append(st)
             lay = L[k]
             src = Src(h.data, (N,) + tuple(lay.in_dims), h.C, scale=st['scale'], shift=st['shift'], act=ACT_LRELU,
@@ -1069,8 +1028,8 @@ class PatchGAN:
             else:
                 h = Act(ar, N, lay.out_dims, lay.cout, dtype=self.dtype)
                 prev_drop = drop.get(k)
-                nxt = Nn[k].state(ar, N, mult=prev_drop) if tail else None
-                lay.forward(src, h.data, sums=h.sums, fin=ops.fin_desc(ar, h.count, [Nn[k].job(nxt)]) if tail else None)
+                nxt = Nn[k].state(ar, N, mult=prev_drop)
+                lay.forward(src, h.data, sums=h.sums, fin=ops.fin_desc(ar, h.count, [Nn[k].job(nxt)]))
                 acts.append(h)
         ctx.update(acts=acts, srcs=srcs, sts=sts)
         return ctx

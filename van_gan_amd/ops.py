@@ -325,8 +325,6 @@ PROF: Optional[KernelProfile] = None
 # and the data-gradient chain (dY -> dX -> IN backward -> next layer) are independent, and on the small deep layers either
 # alone leaves most CUs idle.  The side stream waits for the producer of dY; the main stream waits for the side stream
 # before arena memory is recycled (Arena.release) and before the gradients are consumed (side_join).
-LAZY_RELEASE = os.environ.get('VG_LAZY_RELEASE', '1') != '0'
-FORK_SHORT = os.environ.get('VG_FORK_SHORT', '1') != '0'   # forward shortcut branches on the lane's side stream
 FUSE_CONCAT_NORM = os.environ.get('VG_FUSE_CONCAT_NORM', '1') != '0'   # ... and the conv branch's IN backward apply in the same launch
 FUSE_CONCAT = os.environ.get('VG_FUSE_CONCAT', '1') != '0'       # decoder shortcut data gradient + concat backward in one launch (ConvLayer.dgrad_concat)
 BSTAT = os.environ.get('VG_BSTAT', '1') != '0'       # IN-backward statistics with the data-gradient launch (ConvLayer.dgrad(bstat=...))
@@ -363,7 +361,7 @@ class fork_side:
     in the per-launch timing pass and in dry runs."""
 
     def __init__(self):
-        self.on = SIDE is not None and PROF is None and DRY is None and FORK_SHORT
+        self.on = SIDE is not None and PROF is None and DRY is None
         self.cur = self.sd = self.ctx = None
 
     def __enter__(self):
@@ -465,10 +463,6 @@ class Arena:
         if slot == 0:
             self._pairs[key] = []
 
-    def pair_resume(self, key, slot: int):
-        """Continue the sequence of (key, slot) after other allocations (two forward passes enqueued alternately)."""
-        self._pair = (key, slot)
-
     def pair_end(self):
         self._pair = None
 
@@ -559,7 +553,7 @@ class Arena:
         reading them on a side stream, the memory is simply NOT recycled before the next reset() -- joining the side stream here
         stalled the data-gradient chain behind every block's weight gradients (each lane idle 45 % of a step in the kernel trace);
         the workspace is sized for it (a few GB more at 128^3, of 288)."""
-        if defer and LAZY_RELEASE and self.lazy_ok and SIDE is not None and PROF is None and DRY is None:
+        if defer and self.lazy_ok and SIDE is not None and PROF is None and DRY is None:
             return
         side_join()                 # weight gradients on the side stream may still read the buffers being recycled
         self.off = mark
@@ -1315,11 +1309,8 @@ def in_finalize(sums0, c0, count0, gamma, beta, N, scale, shift, mean=None, rstd
                              N, IN_EPS, _p(scale), _p(shift), _p(mean), _p(rstd), stream()), 'vg_in_finalize')
 
 
-FIN_TAIL = os.environ.get('VG_FIN_TAIL', '1') != '0'     # InstanceNorm finalisation by the producing launch's last workgroup (vg_fin_desc)
-
-
 def fin_desc(ar: 'Arena', count: float, jobs) -> FinDesc:
-    """vg_fin_desc of a producing launch: jobs = [(gamma, beta, mult, state, c_off, c_tot)], state = {'scale', 'shift', 'mean', 'rstd'}
+    """vg_fin_desc of a producing launch (InstanceNorm finalisation by the launch's last workgroup): jobs = [(gamma, beta, mult, state, c_off, c_tot)], state = {'scale', 'shift', 'mean', 'rstd'}
     tensors [N, c_tot] of the consuming norm.  The ticket word comes from the arena's zero pool (cleared once per step)."""
     f = FinDesc()
     tk = ar.alloc((1,), torch.int32, zero=True)

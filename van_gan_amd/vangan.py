@@ -24,40 +24,9 @@ from .ops import Arena
 
 RESULT_KEYS = ['total_IS_loss', 'total_SI_loss', 'D_I_loss', 'D_S_loss', 'gen_IS_loss', 'gen_SI_loss',
                'cycle_gen_SIS_loss', 'cycle_gen_ISI_loss', 'seg_loss', 'reconstruction_loss_I']
-_BFIRST = int(os.environ.get('VG_BFIRST', '5'))       # re-swept with the paired sweeps: 0: 22.27, 4: 21.98, 5: 21.83 ms
-_NOJOIN = os.environ.get('VG_NOJOIN', '1') != '0'
-_LAZY_AR = os.environ.get('VG_LAZY_AR', '1') != '0'
 _INLINE_ENV = os.environ.get('VG_WGRAD_INLINE')
 _INLINE = int(_INLINE_ENV) if _INLINE_ENV is not None else 0      # encoder blocks <= this and the stem; round 3 (DMA weight gradients): off 24.96, 1: 24.92, 2: 24.74, 3: 24.59, 4: 24.62 ms; round 4, final kernels, alternating: 2: 18.85 / 18.88 / 18.87, 3: 18.99 / 18.91 / 19.01; round 5 (wgrad_thin: the side streams are no longer behind at the end of a sweep), same box: -1: 17.78 / 17.79 / 17.94, 0: 17.84 / 17.89 / 17.89, 1: 17.82 / 17.92 / 17.96, 2: 17.93 / 17.97 / 18.08, 3: 17.95 / 18.00, 4: 18.07 / 18.08; the data-parallel schedule (all-reduce of a bucket behind the side stream's weight gradients) wants 1: 18.08 / 18.08 against 18.21 / 18.26 for 0 and 18.09 / 18.11 for 2 -- VanGan.__init__ picks 1 when it synchronises gradients
 _PAIR_BWD = os.environ.get('VG_PAIR_BWD', '1') != '0'       # one 2B-sample backward sweep per generator (both applications) instead of two
-_AR_SPLIT = os.environ.get('VG_AR_SPLIT', '1') != '0'       # world > 1: a generator's finished gradient suffix is all-reduced while its sweep still runs
-_SKEL_BWD_A = int(os.environ.get('VG_SKEL_BWD_A', '0'))      # clDice backward on lane A: 1 before its discriminator sweeps, 2 right before its generator sweep
-_D_ONE_SWEEP = os.environ.get('VG_D_ONE_SWEEP', '1') != '0'    # one 3B-sample backward sweep per discriminator (PatchGAN.backward_both) instead of a 2B and a B sweep
-_SKEL_FWD_A = os.environ.get('VG_SKEL_FWD_A', '0') != '0'    # the predicted skeleton's forward pass on lane A (behind lane B's min-max of cycled_S)
-_SKEL_AUX = os.environ.get('VG_SKEL_AUX', '0') != '0'        # clDice backward from codes filed by the forward pass (streaming launches) instead of re-scanning
-_EARLY_ADAM_DDP = os.environ.get('VG_EARLY_ADAM_DDP', '1') != '0'     # ... under gradient synchronisation too, behind the suffix's early all-reduce
-_EARLY_ADAM = os.environ.get('VG_EARLY_ADAM', '1') != '0'     # a generator's finished parameter suffix (enc4 ... output head, 91 %) is updated and repacked while its sweep still runs
-_INTERLEAVE = os.environ.get('VG_INTERLEAVE', '0') != '0'   # the two lanes' enqueue sequences alternate block by block on the host: measured neutral (21.69 vs 21.63 ms), off
-
-
-def interleave(*seqs, on=True):
-    """seqs: (stream context factory, generator).  Steps the generators alternately, each inside its stream context, until all
-    are exhausted; returns their values.  on=False: one after the other."""
-    vals = [None] * len(seqs)
-    live = list(range(len(seqs)))
-    while live:
-        for i in list(live):
-            ctxf, gen = seqs[i]
-            with ctxf():
-                try:
-                    while True:
-                        next(gen)
-                        if on:
-                            break
-                except StopIteration as e:
-                    vals[i] = e.value
-                    live.remove(i)
-    return vals
 NETS = ['gen_IS', 'gen_SI', 'disc_I', 'disc_S']
 # roctx range (VG_ROCTX=1) opened when a milestone of _mark() has been enqueued: the name of what the host enqueues NEXT
 _PHASE_AFTER = {'A start': 'enqueue: generators, first application (both lanes)', 'A G1 fwd': 'enqueue: lane B event', 'B G1 fwd': 'enqueue: generators, cycle application',
@@ -196,40 +165,31 @@ class VanGan:
         S = self.dims[0] * self.dims[1] * self.dims[2]
         if arena_bytes is None:
             # bytes per voxel: measured peak of one train step with the deferred release of backward temporaries (ops.Arena.release)
-            arena_bytes = int(batch_size * S * (8000 if ops.LAZY_RELEASE else 5200) * (2 if precision == 'fp32' else 1)) + (512 << 20)
+            arena_bytes = int(batch_size * S * 8000 * (2 if precision == 'fp32' else 1)) + (512 << 20)
         self.arena = Arena(arena_bytes, self.device)
         # weight gradients go to a side stream of the stream that issues them (one per lane): within a layer they are
         # independent of the data-gradient chain.  36.9 vs 37.6 ms/step; a single side stream shared by both lanes cost 2 ms.
         ops.side_enable(self.device, os.environ.get('VG_SIDE_STREAM', '1') != '0')
-        # Streams, in a DELIBERATE creation order (VG_STREAM_ORDER): HIP serves the streams of a process from GPU_MAX_HW_QUEUES (4)
-        # hardware queues handed out in creation order, and streams that share a queue run one after the other.
-        # Roles: lane_b (the second forward / backward lane; the first is the caller's current stream), opt (optimizer stream),
-        # side_a / side_b (weight-gradient side streams of the two lanes), comm (gradient all-reduce, data-parallel runs only).  The
-        # first four are the single-GPU set; the communication of a data-parallel run comes LAST so that it never displaces one of
-        # them -- and by default it is not a stream of its own at all: the all-reduce of a bucket is queued on the optimizer stream
-        # (VG_COMM_ON_OPT=0: own stream), in front of the optimizer step that is its only consumer; RCCL's internal stream (created by
-        # the first collective, the rank-0 weight broadcast) then is the fifth and only extra one.
-        lanes = os.environ.get('VG_LANES', '1') != '0'
+        # Streams, in a DELIBERATE creation order -- lane_b, opt, side_b, side_a: HIP serves the streams of a process from
+        # GPU_MAX_HW_QUEUES (4) hardware queues handed out in creation order, and streams that share a queue run one after the other
+        # (DESIGN 6.18).  Roles: lane_b (the second forward / backward lane; the first is the caller's current stream), opt (optimizer
+        # stream), side_b / side_a (weight-gradient side streams of the two lanes).  A data-parallel run adds no stream of its own: the
+        # all-reduce of a bucket is queued on the optimizer stream, in front of the optimizer step that is its only consumer, so it
+        # never displaces one of the four; RCCL's internal stream (created by the first collective, the rank-0 weight broadcast) then is
+        # the fifth and only extra one.
         self._lane_b = self._opt = None
-        self.ddp = self.pg is not None or (os.environ.get('VG_FAKE_AR', '0') == '1')
-        comm = None
-        for role in os.environ.get('VG_STREAM_ORDER', 'lane_b,opt,side_b,side_a,comm').split(','):
-            if role == 'lane_b' and lanes:
-                # forward lanes: the I->S->I chain (G_IS(real_I), G_SI(fake_S), D_S, cycle losses on cycled_I) and the S->I->S chain
-                # are independent until the backward sweeps, so they run on two streams and fill each other's low-occupancy layers
-                self._lane_b = _engine_stream(self.device, 'lane_b')
-            elif role == 'opt' and os.environ.get('VG_OPT_STREAM', '1') != '0':
-                # optimizer stream: a network's clip + Adam + weight repack is queued here as soon as ITS backward sweeps are issued
-                # and waits only for ITS gradient bucket (all-reduce event), while the other networks' backward sweeps still run
-                self._opt = _engine_stream(self.device, 'opt')
-            elif role == 'side_a' and ops.SIDE is not None:
-                ops._side_of(torch.cuda.current_stream(self.device))
-            elif role == 'side_b' and ops.SIDE is not None and self._lane_b is not None:
+        if os.environ.get('VG_LANES', '1') != '0':
+            # forward lanes: the I->S->I chain (G_IS(real_I), G_SI(fake_S), D_S, cycle losses on cycled_I) and the S->I->S chain
+            # are independent until the backward sweeps, so they run on two streams and fill each other's low-occupancy layers
+            self._lane_b = _engine_stream(self.device, 'lane_b')
+        if os.environ.get('VG_OPT_STREAM', '1') != '0':
+            # optimizer stream: a network's clip + Adam + weight repack is queued here as soon as ITS backward sweeps are issued
+            # and waits only for ITS gradient bucket (all-reduce event), while the other networks' backward sweeps still run
+            self._opt = _engine_stream(self.device, 'opt')
+        if ops.SIDE is not None:
+            if self._lane_b is not None:
                 ops._side_of(self._lane_b)
-            elif role == 'comm' and self.ddp and not (self._opt is not None and os.environ.get('VG_COMM_ON_OPT', '1') != '0'):
-                comm = _engine_stream(self.device, 'comm')
-        if self.ddp and comm is None:
-            comm = self._opt                 # None (VG_OPT_STREAM=0): GradSync makes its own
+            ops._side_of(torch.cuda.current_stream(self.device))
         # second workspace for lane B's backward temporaries (bump allocators cannot interleave mark/release)
         self.arena_b = Arena(arena_bytes // 2, self.device) if self._lane_b is not None else None
         # one arena for every backward sweep (VG_LANES=0): the workspace is sized for the two-lane layout, so backward temporaries
@@ -237,15 +197,15 @@ class VanGan:
         self.arena.lazy_ok = self._lane_b is not None
         bcast = {k: s.w for k, s in self.stores.items()}
         bcast.update({k + '.sn_u': s.state for k, s in self.stores.items() if s.state.numel()})      # rank 0's u as well: replicas never exchange it again
-        self.sync = GradSync({k: s.g for k, s in self.stores.items()}, self.pg, bcast, stream=comm)
+        self.sync = GradSync({k: s.g for k, s in self.stores.items()}, self.pg, bcast, stream=self._opt)      # (None, VG_OPT_STREAM=0: GradSync makes its own)
         self.ddp = self.sync.active
         self._inline = _INLINE if (_INLINE_ENV is not None or not self.ddp) else 1      # (see _INLINE)
         self._tl = [] if os.environ.get('VG_TIMELINE') == '1' else None
         self._side_ev = {}
         self._early_tab, self._early_done = {}, {}
         # world > 1: the step does not end with a join of the optimizer stream -- the last buckets' all-reduce + Adam + repack run
-        # under the head of the NEXT step, whose consumers wait for the update event of the network they read (VG_XSTEP=0: join)
-        self._xstep = (self.ddp or os.environ.get('VG_XSTEP_SINGLE', '0') == '1') and self._opt is not None and os.environ.get('VG_XSTEP', '1') != '0'
+        # under the head of the NEXT step, whose consumers wait for the update event of the network they read
+        self._xstep = self.ddp and self._opt is not None
         self._upd_ev = {}
         self._cap = None                 # _StepParams while a train step is being captured into a HIP graph (capture_train_step)
         self._graph = None
@@ -404,7 +364,7 @@ class VanGan:
         pair = do_backward and _PAIR_BWD and self.generator == 'resUnet'       # (the ResNet generator: one B-sample sweep per application)
         gdrop = (drop or {}) if self.generator == 'resnet' else {}
         def fwd(gen, key, slot, x, y):
-            """A generator application as a resumable enqueue sequence; its allocations go to the paired slot (key, slot)."""
+            """A generator application, enqueued on the current stream; its allocations go to the paired slot (key, slot)."""
             if self.generator == 'resnet':
                 # SpatialDropout3D of generator.py:44 / downsample(): per-application channel masks (training only); a test may hand
                 # them in as drop['G_IS.a'] ... (application names of oracle.compute_losses)
@@ -412,39 +372,29 @@ class VanGan:
                 if app in gdrop:
                     gd = gdrop[app]
                 elif training and noise is None and self.dropout_rate > 0:
-                    gd = lambda: self._make_gen_drop(B, ar)           # drawn when the application is enqueued, on ITS lane's stream
+                    gd = self._make_gen_drop(B, ar)           # drawn when the application is enqueued, on ITS lane's stream
                 else:
                     gd = None
-                it = gen.forward_iter(ar, x, y, gd)
-            else:
-                it = gen.forward_iter(ar, x, y)
+                return gen.forward(ar, x, y, gd)
             if pair:
-                ar.pair_begin(key, slot); ar.pair_end()
-            def steps():
-                while True:
-                    if pair:
-                        ar.pair_resume(key, slot)
-                    try:
-                        next(it)
-                    except StopIteration as e:
-                        return e.value
-                    finally:
-                        ar.pair_end()
-                    yield
-            return steps()
-        # (VG_INTERLEAVE=1 enqueues the two lanes' sequences ALTERNATELY, block by block -- the idea: enqueued one after the other, the
-        # second lane's stream sits empty for the first one's enqueue time.  Measured neutral: the host runs far enough ahead.)
+                ar.pair_begin(key, slot)
+            ctx = gen.forward(ar, x, y)
+            if pair:
+                ar.pair_end()
+            return ctx
         self._need('gen_IS'); self._need('gen_SI')
         with laneB():
             self._need('gen_SI'); self._need('gen_IS')
-        c1, c2 = interleave((contextlib.nullcontext, fwd(self.gen_IS, 'gen_IS', 0, rI, fake_S)),       # vangan.py:295   (lane A)
-                            (laneB, fwd(self.gen_SI, 'gen_SI', 0, rS, fake_I)), on=_INTERLEAVE)           # :297            (lane B)
+        c1 = fwd(self.gen_IS, 'gen_IS', 0, rI, fake_S)            # vangan.py:295   (lane A)
+        with laneB():
+            c2 = fwd(self.gen_SI, 'gen_SI', 0, rS, fake_I)        # :297            (lane B)
         self._mark('A G1 fwd')
         with laneB():
             ev_fakeI = ops.record_event(lane_b) if lane_b is not None else None
             self._mark('B G1 fwd')
-        c4, c3 = interleave((contextlib.nullcontext, fwd(self.gen_SI, 'gen_SI', 1, fake_S, cyc_I)),     # :305            (lane A)
-                            (laneB, fwd(self.gen_IS, 'gen_IS', 1, fake_I, cyc_S)), on=_INTERLEAVE)        # :300            (lane B)
+        c4 = fwd(self.gen_SI, 'gen_SI', 1, fake_S, cyc_I)         # :305            (lane A)
+        with laneB():
+            c3 = fwd(self.gen_IS, 'gen_IS', 1, fake_I, cyc_S)     # :300            (lane B)
         self._mark('A G2 fwd')
         with laneB():
             self._mark('B G2 fwd')
@@ -454,43 +404,23 @@ class VanGan:
 
         # ---- cycle / segmentation losses on cycled_S (loss_functions.py:185-190, 211-226): lane B; target skeleton: lane A ----
         imgs_t, skels_t = ar.alloc((it + 2,) + vol, f32), ar.alloc((it + 1,) + vol, f32)
-        # VG_SKEL_FWD_A: the PREDICTED skeleton's forward pass on lane A as well (behind lane B's min-max normalisation of cycled_S) -- lane B
-        # is the longer lane; its clDice then starts from the finished skeletons
-        skel_fwd_on_a = _SKEL_FWD_A and lane_b is not None
-        ev_ncS = None
-        if skel_fwd_on_a:
-            with laneB():
-                ops.wait_event(lane_b, ev_nS)
-                mmcS = ar.alloc((B, 4), f32)
-                ncS = ar.alloc(vol, f32)
-                ops.minmax(cyc_S, B, S, mmcS); ops.minmax_apply(cyc_S, mmcS, B, S, ncS)
-                ev_ncS = ops.record_event(lane_b)
         ops.soft_skel_fwd(nS, dims4, it, imgs_t, skels_t)                                # lane A
-        if skel_fwd_on_a:
-            imgs_p, skels_p = ar.alloc((it + 2,) + vol, f32), ar.alloc((it + 1,) + vol, f32)
-            aux_p = ar.alloc((ops.skel_aux_bytes(dims4, it),), torch.uint8) if (do_backward and _SKEL_AUX) else None
-            ops.wait_event(main, ev_ncS)
-            ops.soft_skel_fwd(ncS, dims4, it, imgs_p, skels_p, aux_p)                    # lane A
         ev_skel_t = ops.record_event(main) if lane_b is not None else None
         self._mark('A target skeleton')
         with laneB():
-            if not skel_fwd_on_a:
-                if lane_b is not None:
-                    ops.wait_event(lane_b, ev_nS)
-                mmcS = ar.alloc((B, 4), f32)
-                ncS = ar.alloc(vol, f32)
-                ops.minmax(cyc_S, B, S, mmcS); ops.minmax_apply(cyc_S, mmcS, B, S, ncS)
+            if lane_b is not None:
+                ops.wait_event(lane_b, ev_nS)
+            mmcS = ar.alloc((B, 4), f32)
+            ncS = ar.alloc(vol, f32)
+            ops.minmax(cyc_S, B, S, mmcS); ops.minmax_apply(cyc_S, mmcS, B, S, ncS)
             g_ncS = ar.alloc(vol, f32) if do_backward else None
             sis_bce = self.cycle_loss_SIS == 'bce'
             if sis_bce:
                 ops.bce(nS, ncS, acc[0:1], self._cycle_scale('SIS', B, S), g_ncS, accumulate=False)
             elif not do_backward:                # MAE / MSE / L4 on the RAW volumes (loss_functions.py:177-184); the min-max stays for clDice
                 ops.lp_loss(rS, cyc_S, LP_ORDER[self.cycle_loss_SIS], acc[0:1])
-            if not skel_fwd_on_a:
-                imgs_p, skels_p = ar.alloc((it + 2,) + vol, f32), ar.alloc((it + 1,) + vol, f32)
-                # the predicted skeleton is differentiated: its forward pass files delta and the pooling arg-extrema codes (6 B per voxel and step)
-                aux_p = ar.alloc((ops.skel_aux_bytes(dims4, it),), torch.uint8) if (do_backward and _SKEL_AUX) else None
-                ops.soft_skel_fwd(ncS, dims4, it, imgs_p, skels_p, aux_p)
+            imgs_p, skels_p = ar.alloc((it + 2,) + vol, f32), ar.alloc((it + 1,) + vol, f32)
+            ops.soft_skel_fwd(ncS, dims4, it, imgs_p, skels_p)
             if lane_b is not None:
                 ops.wait_event(lane_b, ev_skel_t)
             skel_p, skel_t = skels_p[it], skels_t[it]
@@ -498,24 +428,17 @@ class VanGan:
             coef = ar.alloc((8,), f32, zero=True)
             ops.dot_sums(skel_p, nS, sums[0:3]); ops.dot_sums(skel_t, ncS, sums[3:6]); ops.dot_sums(nS, ncS, sums[6:9])
             ops.cldice_coef(sums, self.lambda_topology / self.n_devices, 0.5, coef)
-            def cldice_backward():
+            if do_backward:
                 gskel = ar.alloc(vol, f32)
                 ops.cldice_grads(nS, skel_t, coef, gskel, g_ncS, accumulate=sis_bce)      # (without the BCE term: the first writer of g_ncS)
-                work = ar.alloc((4,) + vol, f32)
-                ops.soft_skel_bwd(imgs_p, skels_p, gskel, dims4, it, work, g_ncS, aux_p)
+                work = ar.alloc((4,) + vol, f32)                  # (the re-scanning backward uses three of the four volumes)
+                ops.soft_skel_bwd(imgs_p, skels_p, gskel, dims4, it, work, g_ncS)
                 tmp2 = ar.alloc((B, 2), f32, zero=True)
                 ops.minmax_bwd(cyc_S, ncS, g_ncS, mmcS, B, S, tmp2, gS2[B:])
                 if not sis_bce:
-                    # the raw-volume cycle term adds its gradient DIRECTLY to d cycled_S, behind the min-max backward that writes the
-                    # buffer -- same function, so same stream, whichever lane VG_SKEL_BWD_A puts this on (no event of its own)
+                    # the raw-volume cycle term adds its gradient DIRECTLY to d cycled_S, behind the min-max backward that writes the buffer
                     ops.lp_loss(rS, cyc_S, LP_ORDER[self.cycle_loss_SIS], acc[0:1], self._cycle_scale('SIS', B, S), gS2[B:], accumulate=True)
             g_cS = gS2[B:] if do_backward else None
-            # VG_SKEL_BWD_A: the skeleton's backward (34 launches whose result only lane A's generator sweep consumes) on lane A, behind
-            # an event of lane B's clDice forward -- lane B is the longer lane (tools/timeline.py: lane A ends 1.2 ms before it)
-            skel_bwd_on_a = do_backward and _SKEL_BWD_A and lane_b is not None
-            ev_cldice = ops.record_event(lane_b) if skel_bwd_on_a else None
-            if do_backward and not skel_bwd_on_a:
-                cldice_backward()
             self._mark('B clDice')
 
         # ---- cycle MSE + SSIM reconstruction on cycled_I (loss_functions.py:179-180, 193-208) ----
@@ -569,7 +492,7 @@ class VanGan:
         gd = self._adv_scale(B, nps)
         adv = self._adv_term
         # upstream gradients at the patch logits, adjacent: [d critic loss (2B: real, fake); d generator loss (B: fake)] -- one 3B-sample
-        # backward sweep per discriminator reads them as one tensor (VG_D_ONE_SWEEP)
+        # backward sweep per discriminator reads them as one tensor
         gS3 = ar.alloc((3 * B,) + tuple(logS.shape[1:]), f32) if do_backward else None
         gI3 = ar.alloc((3 * B,) + tuple(logI.shape[1:]), f32) if do_backward else None
         gS_D, gI_D = (gS3[:2 * B], gI3[:2 * B]) if do_backward else (None, None)
@@ -601,18 +524,14 @@ class VanGan:
             adv(logI[:B], 1.0, acc[7:8], 0.5 * gd, None if gI_D is None else gI_D[:B])
             adv(logI[B:], 0.0, acc[8:9], 0.5 * gd, None if gI_D is None else gI_D[B:])
         self._mark('A D fwd')
-        if skel_bwd_on_a and _SKEL_BWD_A == 1:
-            ops.wait_event(main, ev_cldice)
-            cldice_backward()
-        # No full join before the backward sweeps (VG_NOJOIN): lane A's discriminator sweeps and its adversarial generator sweep need
-        # nothing of lane B; only its cycle sweep (c3 ran on lane B, g_cS comes out of lane B's clDice) waits for lane B's forward.
-        nojoin = lane_b is not None and do_backward and _NOJOIN
+        # No full join before the backward sweeps: lane A's discriminator sweeps and its adversarial generator sweep need nothing of
+        # lane B; only its cycle sweep (c3 ran on lane B, g_cS comes out of lane B's clDice) waits for lane B's forward.
         ev_bfwd = None
         if lane_b is not None:
-            if nojoin:
+            if do_backward:
                 ev_bfwd = ops.record_event(lane_b)
             else:
-                ops.wait_stream(main, lane_b)                                                    # lanes join before the backward sweeps
+                ops.wait_stream(main, lane_b)                                                    # forward only: the lanes join here
 
         self._upd_ev = {}                # every stream that reads weights in this step has queued its waits (main: all four networks)
         if do_backward:
@@ -632,83 +551,46 @@ class VanGan:
                 disc.head_backward(logits, mask, gzd, g_D, wgrad=True)                                   # critic loss: [real; fake], Dense gradients
                 disc.head_backward(logits[B:], None if mask is None else mask[B:], gzg, g_G, wgrad=False)  # generator loss through the fake half
 
-            def a_disc():
-                if self.wasserstein:
-                    w_head_bwd('S', self.disc_S, logS, gS_D, gS_G)
-                if _D_ONE_SWEEP:
-                    self.disc_S.backward_both(ar, dS, gS3, B, g_fS)
-                    self._start_allreduce(['disc_S'], lazy=apply)
-                else:
-                    self.disc_S.backward(ar, dS, gS_D, 0, 2 * B, wgrad=True)
-                    self._start_allreduce(['disc_S'], lazy=apply)
-                    self.disc_S.backward(ar, dS, gS_G, B, 2 * B, wgrad=False, dx=g_fS)       # still reads D_S's packed weights
+            def reduce_and_update(name, hi=None):
+                self._start_allreduce([name], lazy=apply, hi=hi)
                 if apply:
-                    self._schedule_update('disc_S')
-                self._mark('A D bwd')
+                    self._schedule_update(name)
 
-            def b_disc():
-                # (Moving D_I's D-loss sweep to lane A, whose sweeps finish 3.7 ms before lane B's, was measured: the main lanes then end
-                # at 26.8 / 23.4 ms but lane A's weight-gradient side stream becomes the tail -- 29.9 vs 29.4 ms per step.)
-                with laneB():
-                    if self.wasserstein:
-                        w_head_bwd('I', self.disc_I, logI, gI_D, gI_G)
-                    if _D_ONE_SWEEP:
-                        self.disc_I.backward_both(arB, dI, gI3, B, g_fI)
-                        self._start_allreduce(['disc_I'], lazy=apply)
-                    else:
-                        self.disc_I.backward(arB, dI, gI_D, 0, 2 * B, wgrad=True)
-                        self._start_allreduce(['disc_I'], lazy=apply)
-                        self.disc_I.backward(arB, dI, gI_G, B, 2 * B, wgrad=False, dx=g_fI)
-                    if apply:
-                        self._schedule_update('disc_I')
-                    self._mark('B D bwd')
+            def disc_bwd(tag, name, disc, dar, dctx, logits, g3, g_f):
+                """A discriminator's 3B-sample sweep on the current stream, then its all-reduce and optimizer step."""
+                if self.wasserstein:
+                    w_head_bwd(tag, disc, logits, g3[:2 * B], g3[2 * B:])
+                disc.backward_both(dar, dctx, g3, B, g_f)
+                reduce_and_update(name)
 
             mk = ar.mark()
             mkb = arB.mark()
-            self._bwd_ctx = {'gen_IS': [c1, c3], 'gen_SI': [c2, c4]}        # what the sweeps store (gradient buffers hang on the Act objects): for tests
-
-            def a_adv():
-                if pair:
-                    return
+            # Host enqueue order: lane B first for the discriminator sweeps and for the generators' last (cycle / paired) sweeps, lane A
+            # first for the unpaired adversarial sweeps.
+            # (Moving D_I's D-loss sweep to lane A, whose sweeps finish 3.7 ms before lane B's, was measured: the main lanes then end
+            # at 26.8 / 23.4 ms but lane A's weight-gradient side stream becomes the tail -- 29.9 vs 29.4 ms per step.)
+            with laneB():
+                disc_bwd('I', 'disc_I', self.disc_I, arB, dI, logI, gI3, g_fI)
+                self._mark('B D bwd')
+            disc_bwd('S', 'disc_S', self.disc_S, ar, dS, logS, gS3, g_fS)
+            self._mark('A D bwd')
+            if not pair:
+                self._bwd_ctx = {'gen_IS': [c1, c3], 'gen_SI': [c2, c4]}        # what the sweeps store (gradient buffers hang on the Act objects): for tests
                 self.gen_IS.backward(ar, c1, g_fS); ar.release(mk, defer=True)        # adversarial application
                 self._mark('A G adv bwd')
-
-            def b_adv():
-                if pair:
-                    return
                 with laneB():
                     self.gen_SI.backward(arB, c2, g_fI); arB.release(mkb, defer=True)
                     self._mark('B G adv bwd')
-
-            def a_cyc():
+                    self.gen_SI.backward(arB, c4, g_cI, inline_from=self._inline); arB.release(mkb, defer=True)    # cycle application
+                    self._mark('B G cyc bwd')
+                    reduce_and_update('gen_SI')
                 if ev_bfwd is not None:
                     ops.wait_event(main, ev_bfwd)                                          # c3 and g_cS are lane B's
-                self.gen_IS.backward(ar, c3, g_cS, inline_from=self._inline); ar.release(mk, defer=True)    # cycle application
+                self.gen_IS.backward(ar, c3, g_cS, inline_from=self._inline); ar.release(mk, defer=True)
                 self._mark('A G cyc bwd')
-                self._start_allreduce(['gen_IS'], lazy=apply)
-                if apply:
-                    self._schedule_update('gen_IS')
-
-            def b_cyc():
-                with laneB():
-                    self.gen_SI.backward(arB, c4, g_cI, inline_from=self._inline); arB.release(mkb, defer=True)
-                    self._mark('B G cyc bwd')
-                    self._start_allreduce(['gen_SI'], lazy=apply)
-                    if apply:
-                        self._schedule_update('gen_SI')
-
-            # host enqueue order per stage (bit i of VG_BFIRST: lane B's sweep of stage i is enqueued before lane A's)
-            stages = ((a_disc, b_disc), (a_adv, b_adv)) if pair else ((a_disc, b_disc), (a_adv, b_adv), (a_cyc, b_cyc))
-            for i, (fa, fb) in enumerate(stages):
-                if (_BFIRST >> i) & 1:
-                    fb(); fa()
-                else:
-                    fa(); fb()
-            if pair:
-                # the generators' 2B-sample sweeps over both applications ([adversarial; cycle]), enqueued alternately block by block
-                if skel_bwd_on_a and _SKEL_BWD_A == 2:
-                    ops.wait_event(main, ev_cldice)
-                    cldice_backward()
+                reduce_and_update('gen_IS')
+            else:
+                # the generators' 2B-sample sweeps over both applications ([adversarial; cycle])
                 if ev_bfwd is not None:
                     ops.wait_event(main, ev_bfwd)                                          # c3 and g_cS are lane B's
                 ccA = pair_ctx(ar, c1, bufI, (fake_S, cyc_S), self.gen_IS.lv[0])
@@ -716,36 +598,27 @@ class VanGan:
                 self._bwd_ctx = {'gen_IS': [ccA], 'gen_SI': [ccB]}
                 # data parallel: the finished suffix of a generator's gradient bucket (enc4 ... output head, 34 of 38 MB) goes to the
                 # all-reduce when the sweep has passed enc4 -- with ~40 % of the sweep still ahead; only the last 4 MB wait for its end
-                split = self.ddp and apply and _AR_SPLIT
-                early_adam = (_EARLY_ADAM and apply and self._opt is not None and self._cap is None and ops.PROF is None
-                              and ops.DRY is None and ops.REC is None and (not self.ddp or _EARLY_ADAM_DDP))
+                split = self.ddp and apply
+                # ... and the suffix's parameters (91 %) are updated and repacked then, while the sweep still runs -- in the eager step only
+                early_adam = (apply and self._opt is not None and self._cap is None and ops.PROF is None and ops.DRY is None
+                              and ops.REC is None)
                 def early(name, gen):
-                    ea = early_adam and hasattr(gen, 'grad_suffix_offset')
-                    if split:
-                        def f():
+                    def f():
+                        if split:
                             self._start_allreduce([name], lazy=apply, lo=gen.grad_suffix_offset())
-                            if ea:
-                                self._early_update(name)         # behind the suffix's all-reduce (queued on / awaited by the optimizer stream)
-                        return f
-                    if ea and not self.ddp:
-                        return lambda: self._early_update(name)
-                    return None
-                order = ((laneB, self.gen_SI.backward_iter(arB, ccB, gI2, inline_from=self._inline, on_suffix_done=early('gen_SI', self.gen_SI))),
-                         (contextlib.nullcontext, self.gen_IS.backward_iter(ar, ccA, gS2, inline_from=self._inline, on_suffix_done=early('gen_IS', self.gen_IS))))
-                interleave(*(order if (_BFIRST >> 2) & 1 else order[::-1]), on=_INTERLEAVE)
-                hiA = self.gen_IS.grad_suffix_offset() if split else None
-                hiB = self.gen_SI.grad_suffix_offset() if split else None
+                        if early_adam:
+                            self._early_update(name)         # behind the suffix's all-reduce (queued on / awaited by the optimizer stream)
+                    return f if (split or early_adam) else None
+                with laneB():
+                    self.gen_SI.backward(arB, ccB, gI2, inline_from=self._inline, on_suffix_done=early('gen_SI', self.gen_SI))
+                self.gen_IS.backward(ar, ccA, gS2, inline_from=self._inline, on_suffix_done=early('gen_IS', self.gen_IS))
                 ar.release(mk, defer=True)
                 self._mark('A G cyc bwd')
-                self._start_allreduce(['gen_IS'], lazy=apply, hi=hiA)
-                if apply:
-                    self._schedule_update('gen_IS')
+                reduce_and_update('gen_IS', self.gen_IS.grad_suffix_offset() if split else None)
                 with laneB():
                     arB.release(mkb, defer=True)
                     self._mark('B G cyc bwd')
-                    self._start_allreduce(['gen_SI'], lazy=apply, hi=hiB)
-                    if apply:
-                        self._schedule_update('gen_SI')
+                    reduce_and_update('gen_SI', self.gen_SI.grad_suffix_offset() if split else None)
             if lane_b is not None:
                 with laneB():
                     ops.side_join()                 # lane B's weight gradients (its lane no longer waits for them on the way)
@@ -804,7 +677,7 @@ class VanGan:
         issued so far.  lazy (an optimizer step follows on the optimizer stream): the lane itself does not wait for its side
         stream -- the all-reduce stream and the optimizer stream do (it used to stall, e.g. between the two discriminator sweeps,
         until the discriminator's weight gradients had finished)."""
-        if lazy and self._opt is not None and ops.PROF is None and _LAZY_AR:
+        if lazy and self._opt is not None and ops.PROF is None:
             ev = ops.side_event()
             for n in names:
                 self._side_ev[n] = ev
