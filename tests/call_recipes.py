@@ -44,6 +44,34 @@ def needed_fin():
     return sorted({(v, fin_shape(r)) for cfg in LR.NEEDED for k, _, v, r in all_walks()[cfg][0] if k == 'fwd' and r.get('fin')})
 
 
+def inference_needed_fin():
+    """Every (forward variant, tail job shape) of the two NEEDED inference walks (layer_recipes.INFER_NEEDED)."""
+    walks = LR.all_inference_walks()
+    return sorted({(v, fin_shape(r)) for cfg in LR.INFER_NEEDED for k, _, v, r in walks[cfg][0] if k == 'fwd' and r.get('fin')})
+
+
+@functools.lru_cache(maxsize=None)
+def inference_fin_cases() -> Dict[str, dict]:
+    """case id -> run_fin case for every (forward variant, tail job shape) of the inference walks that the train steps' needed_fin() does
+    not have: the cheapest recorded call with that tail over all inference walks, shrunk like its convolution's representative
+    (layer_recipes.shrink_recipe: identical variant string, the tail's voxel count follows the grid)."""
+    have = set(needed_fin())
+    want = [k for k in inference_needed_fin() if k not in have]
+    cases: Dict[str, dict] = {}
+    for cfg, (recs, _) in LR.all_inference_walks().items():
+        for kind, layer, v, r in recs:
+            if kind != 'fwd' or not r.get('fin') or (v, fin_shape(r)) not in want:
+                continue
+            cid = 'fin %s jobs=%s' % (v, fin_shape(r))
+            m = LR.recipe_macs(r)
+            if cid not in cases or m < cases[cid]['macs']:
+                cases[cid] = dict(kind='fin', recipe=r, variant=v, config=cfg, layer=layer, macs=m, covers=[('fin', v, fin_shape(r))])
+    for c in cases.values():
+        c['recipe'] = LR.shrink_recipe(c['recipe'], c['variant'])
+        c['macs'] = LR.recipe_macs(c['recipe'])
+    return cases
+
+
 def decoder_blocks(cfg) -> List[dict]:
     """The decoder blocks' fused backward launches of one config: dec0-dec3 with the shortcut's c_low (upsampled source), c_skip, cout,
     the block's level dims and the 2B samples of the generator's backward sweep (the two applications are one sweep)."""

@@ -112,10 +112,130 @@ def needed_variants(precision='bf16'):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# the sliding-window inference forward: ResUNet.forward(save=False) on window batches (VanGan.stitch_subvolumes)
+# ----------------------------------------------------------------------------------------------------------------------
+# name -> (window dims, windows per batch).  The first two are what the published inference line runs (128^3 windows, two per batch,
+# and the one-window tail batch of an odd window count); the small ones only donate cheaper representatives, as '32^3 B1' does above.
+INFER_CONFIGS = {
+    'infer 128^3 N2': ((128, 128, 128), 2),
+    'infer 128^3 N1': ((128, 128, 128), 1),
+    'infer 64^3 N2': ((64, 64, 64), 2),
+    'infer 32^3 N2': ((32, 32, 32), 2),
+}
+INFER_NEEDED = ('infer 128^3 N2', 'infer 128^3 N1')
+
+
+def walk_inference(dims, N, dtype=torch.bfloat16):
+    """-> ([(kind, layer name, variant, recipe)], [(entry point, regime)]) of ONE forward-only application of the ResUNet generator on
+    N windows, as the sliding-window path runs it (block temporaries recycled).  dtype: the network's storage type (torch.float16 is
+    the libvangan_hip_h.so engine; the dispatch is host logic shared by both builds)."""
+    from van_gan_amd import ops
+    from van_gan_amd.nets import ParamStore, ResUNet, gen_param_specs
+    G = ResUNet(ParamStore(gen_param_specs(), 'cpu'), dims, dtype)
+    ar = ops.Arena(int(N * dims[0] * dims[1] * dims[2] * 5200) + (512 << 20), 'cpu')     # never touched: dry runs do not write
+    with ops.DryRun() as dry:
+        x, y = ar.alloc((N,) + tuple(dims) + (1,), torch.float32), ar.alloc((N,) + tuple(dims) + (1,), torch.float32)
+        G.forward(ar, x, y, save=False)
+    return [(k, n, v, r) for (k, n, v), r in zip(dry.records, dry.recipes)], list(dry.calls)
+
+
+@functools.lru_cache(maxsize=None)
+def all_inference_walks():
+    return {name: walk_inference(dims, N) for name, (dims, N) in INFER_CONFIGS.items()}
+
+
+def inference_needed_variants():
+    walks = all_inference_walks()
+    return sorted({(k, v) for cfg in INFER_NEEDED for (k, _, v, _) in walks[cfg][0]})
+
+
+def recipe_variant(recipe) -> str:
+    """The variant a recorded FORWARD call selects, by a CPU dry run of the rebuilt call (no contents: empty tensors)."""
+    from van_gan_amd.ops import Src
+    assert recipe['kind'] == 'fwd'
+    L, sr = recipe['layer'], recipe['src']
+    _, lay = make_layer_from(L, 'cpu')
+    N, dims, c0, c1, sh = sr['N'], tuple(sr['dims']), sr['c0'], sr['c1'], sr['shift0']
+    e = lambda *shp, dt=torch.bfloat16: torch.empty(*shp, dtype=dt)
+    src = Src(e(N, *[n >> sh for n in dims], c0, dt=torch.float32 if sr['f32'] else torch.bfloat16), (N,) + dims, c0,
+              e(N, *dims, c1) if c1 else None, c1, shift0=sh, f32=sr['f32'],
+              scale=e(N, c0 + c1, dt=torch.float32) if sr['affine'] else None, shift=e(N, c0 + c1, dt=torch.float32) if sr['affine'] else None,
+              act=sr['act'], noise=e(N, *[n + 2 * sr['noise_pad'] for n in dims], c0 + c1) if sr['noise'] else None, noise_pad=sr['noise_pad'])
+    out = e(N, *lay.out_dims, L['cout'], dt=torch.float32 if recipe['out_f32'] else torch.bfloat16)
+    pc = lambda: e(N, L['cout'], dt=torch.float32)
+    got = dry_variants(lambda: lay.forward(src, out, sums=e(8, N, L['cout'], 2, dt=torch.float32) if recipe['sums'] else None,
+                                           res=e(N, *lay.out_dims, L['cout']) if recipe['res'] else None,
+                                           res_scale=pc() if recipe['res'] else None, res_shift=pc() if recipe['res'] else None, tanh=recipe['tanh']))
+    assert len(got) == 1
+    return got[0]
+
+
+SHRINK_ABOVE = 1e9          # MACs: cheaper calls are replayed as recorded (a shrunk grid has fewer tiles and fewer workgroups)
+
+
+def shrink_recipe(recipe, variant):
+    """A cheaper forward call of the same layer that selects the IDENTICAL variant string: one sample instead of several, axes halved
+    (greedily, while the call costs more than SHRINK_ABOVE and the CPU dry run of the shrunk call still reports `variant`).  The recorded finalisation tail keeps its jobs; its
+    voxel count follows the output grid."""
+    def with_shape(r, N, dims):
+        L = dict(r['layer'], in_dims=tuple(dims))
+        out = dict(r, layer=L, src=dict(r['src'], N=N, dims=tuple(dims)))
+        if r.get('fin'):
+            s, k = L['stride'], L['k']
+            od = [(n + 2 - k) // s + 1 if L['pad'] == 'reflect' else -(-n // s) for n in dims]
+            out['fin'] = dict(r['fin'], count=float(math.prod(od)))
+        return out
+
+    best, moved = recipe, True
+    while moved and recipe_macs(best) > SHRINK_ABOVE:
+        moved = False
+        N, dims = best['src']['N'], tuple(best['src']['dims'])
+        tries = [(1, dims)] if N > 1 else []
+        tries += [(N, dims[:a] + (dims[a] // 2,) + dims[a + 1:]) for a in range(3) if dims[a] % 4 == 0 and dims[a] >= 16]
+        for n_, d_ in tries:
+            cand = with_shape(best, n_, d_)
+            try:
+                same = recipe_variant(cand) == variant
+            except Exception:                       # no tile plan for the shrunk grid: not a candidate
+                same = False
+            if same:
+                best, moved = cand, True
+                break
+    return best
+
+
+@functools.lru_cache(maxsize=None)
+def inference_representatives() -> Dict[Tuple[str, str], dict]:
+    """(kind, variant) -> {'recipe', 'config', 'layer', 'macs'} for every variant of the inference walks: the cheapest call over those
+    walks and the training walks, shrunk further where the dispatch keeps the variant (shrink_recipe).  representatives() is not
+    touched: it stays the case list of tests/test_gpu_layers.py."""
+    walks = {cfg: recs for cfg, (recs, _) in all_inference_walks().items()}
+    keys = {(k, v) for recs in walks.values() for (k, _, v, _) in recs}
+    best: Dict[Tuple[str, str], dict] = {}
+    for cfg, recs in list(walks.items()) + list(all_records().items()):
+        for kind, name, variant, recipe in recs:
+            key, m = (kind, variant), recipe_macs(recipe)
+            if key in keys and (key not in best or m < best[key]['macs']):
+                best[key] = dict(recipe=recipe, config=cfg, layer=name, macs=m)
+    for key, b in best.items():
+        r = shrink_recipe(b['recipe'], key[1])
+        if r is not b['recipe']:
+            b.update(recipe=r, macs=recipe_macs(r), shrunk=True)
+    return best
+
+
+def inference_only_variants():
+    """The variants of the two NEEDED inference walks that no train step of BASELINE configs 1-4 selects."""
+    reps = representatives()
+    return sorted(kv for kv in inference_needed_variants() if kv not in reps)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # replaying a recipe on the GPU against the CPU oracle
 # ----------------------------------------------------------------------------------------------------------------------
-def bf(x):
-    return x.to(torch.bfloat16).to(x.dtype)
+def bf(x, storage=torch.bfloat16):
+    """x rounded to the library's 16-bit storage format (bf16; torch.float16 for libvangan_hip_h.so), in x's own dtype."""
+    return x.to(storage).to(x.dtype)
 
 
 def _ref_dtype(macs):
@@ -139,30 +259,30 @@ def make_layer_from(ctor, dev, seed=0, dtype=torch.bfloat16):
     return st, lay
 
 
-def make_operand(sr, pad, dev, g):
-    """Random contents for a Src recipe -> (Src on dev, host tensors)."""
+def make_operand(sr, pad, dev, g, storage=torch.bfloat16):
+    """Random contents for a Src recipe -> (Src on dev, host tensors).  storage: the 16-bit type of the stored tensors."""
     from van_gan_amd.ops import Src
     N, dims, c0, c1, sh = sr['N'], tuple(sr['dims']), sr['c0'], sr['c1'], sr['shift0']
     C_ = c0 + c1
     low = tuple(n >> sh for n in dims)
     x0 = torch.randn(N, *low, c0, generator=g)
-    x0 = x0 if sr['f32'] else x0.to(torch.bfloat16)
-    x1 = torch.randn(N, *dims, c1, generator=g).to(torch.bfloat16) if c1 else None
+    x0 = x0 if sr['f32'] else x0.to(storage)
+    x1 = torch.randn(N, *dims, c1, generator=g).to(storage) if c1 else None
     scale = (torch.rand(N, C_, generator=g) + 0.5) if sr['affine'] else None
     shift = (torch.randn(N, C_, generator=g) * 0.3) if sr['affine'] else None
     noise = None
     if sr['noise']:
         npd = sr['noise_pad']
-        noise = (torch.randn(N, *[n + 2 * npd for n in dims], C_, generator=g) * 0.1).to(torch.bfloat16)
+        noise = (torch.randn(N, *[n + 2 * npd for n in dims], C_, generator=g) * 0.1).to(storage)
     d = lambda t: None if t is None else t.to(dev)
     src = Src(d(x0), (N,) + dims, c0, d(x1), c1, shift0=sh, f32=sr['f32'], scale=d(scale), shift=d(shift), act=sr['act'],
               noise=d(noise), noise_pad=sr['noise_pad'])
     return src, dict(x0=x0, x1=x1, scale=scale, shift=shift, noise=noise)
 
 
-def ref_operand(sr, host, pad, dt):
+def ref_operand(sr, host, pad, dt, storage=torch.bfloat16):
     """The convolution's input as the kernels stage it: act(IN-affine(virtual upsample + concat)) [-> reflection pad]
-    + noise, rounded to bf16.  NCDHW, on the padded grid for 'reflect'."""
+    + noise, rounded to bf16 (to `storage`).  NCDHW, on the padded grid for 'reflect'."""
     from oracle import vangan_oracle as O
     from van_gan_amd import ops
     x = host['x0'].to(dt)
@@ -182,7 +302,7 @@ def ref_operand(sr, host, pad, dt):
         a = O.reflect_pad1(a)
     if host['noise'] is not None:
         a = a + O.to_ncdhw(host['noise'].to(dt))
-    return bf(a)
+    return bf(a, storage)
 
 
 def close_bf16(got, ref, name='', rel=1.2e-2, floor=2e-3):
@@ -206,36 +326,52 @@ def dry_variants(fn):
     return [v for (_, _, v) in dry.records]
 
 
-def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16'):
+# Bounds of a forward replay per storage type: close_bf16's (rel, floor) on a 16-bit output, rel-L2 of the statistics, rel-L2 of an f32
+# output.  bf16: those of tests/test_gpu_ops.py.  fp16: kernel and reference read identical 16-bit-rounded operands, so what differs is
+# the fp32 accumulation order and the ONE rounding of the stored output; fp16 carries 11 significand bits where bf16 carries 8, so every
+# bound that comes from that rounding scales by 2^-3 (tests/test_variant_coverage.py checks on the CPU that a float32 convolution + .half()
+# stays inside it against float64).  The f32-output bound has no 16-bit rounding in it and stays.
+FWD_TOL = {torch.bfloat16: dict(rel=1.2e-2, floor=2e-3, sums=2e-2, f32=1e-4),
+           torch.float16: dict(rel=1.5e-3, floor=2.5e-4, sums=2.5e-3, f32=1e-4)}
+
+
+def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=torch.bfloat16):
     """Replay one recorded call on `dev` with random contents and compare with the oracle.  Tolerances as in
     tests/test_gpu_ops.py: identical bf16-rounded operands into the reference, so only fp32 accumulation order and the one
-    rounding of the stored output differ."""
+    rounding of the stored output differ.
+    storage=torch.float16 (forward calls only, made inside ops.Fp16()): 16-bit tensors are IEEE half, the reference rounds with
+    .half() where it rounds to bf16 otherwise, bounds FWD_TOL[torch.float16]; a single-channel fp32 residual (res_c1, stem.cb) is
+    replayed as recorded.  Returns the measured errors of a forward replay."""
     from oracle import vangan_oracle as O
     L = recipe['layer']
     kind, pad, stride = recipe['kind'], L['pad'], L['stride']
     dt = _ref_dtype(recipe_macs(recipe))
     g = torch.Generator().manual_seed(seed)
-    st, lay = make_layer_from(L, dev)
+    half = storage != torch.bfloat16
+    assert storage in FWD_TOL and (not half or kind == 'fwd')
+    st, lay = make_layer_from(L, dev, dtype=storage)
     lay.pack()
-    w_ref = bf(st.param('c.w').cpu().to(dt))
+    w_ref = bf(st.param('c.w').cpu().to(dt), storage)
     b_ref = st.param('c.b').cpu().to(dt) if L['bias'] else None
     conv_pad = 'valid' if pad == 'reflect' else 'same'
     if kind in ('fwd', 'wgrad'):
         sr = recipe['src']
         N = sr['N']
-        src, host = make_operand(sr, pad, dev, g)
-        ap = ref_operand(sr, host, pad, dt)
+        src, host = make_operand(sr, pad, dev, g, storage)
+        ap = ref_operand(sr, host, pad, dt, storage)
     if kind == 'fwd':
-        odt = torch.float32 if recipe['out_f32'] else torch.bfloat16
+        tol = FWD_TOL[storage]
+        odt = torch.float32 if recipe['out_f32'] else storage
         out = torch.zeros(N, *lay.out_dims, L['cout'], dtype=odt, device=dev)
         sums = torch.zeros(8, N, L['cout'], 2, device=dev) if recipe['sums'] else None
         res = rs = rb = None
+        c1 = half and bool(recipe.get('res_c1'))
         if recipe['res']:
-            res = torch.randn(N, *lay.out_dims, L['cout'], generator=g).to(torch.bfloat16)
+            res = torch.randn(N, *lay.out_dims, 1, generator=g) if c1 else torch.randn(N, *lay.out_dims, L['cout'], generator=g).to(storage)
             rs, rb = torch.rand(N, L['cout'], generator=g) + 0.5, torch.randn(N, L['cout'], generator=g)
         call = lambda: lay.forward(src, out, sums=sums, res=None if res is None else res.to(dev),
                                    res_scale=None if rs is None else rs.to(dev), res_shift=None if rb is None else rb.to(dev),
-                                   tanh=recipe['tanh'])
+                                   tanh=recipe['tanh'], **(dict(res_c1=True) if c1 else {}))
         assert dry_variants(call) == [expect_variant]
         call()
         torch.cuda.synchronize()
@@ -244,15 +380,19 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16'):
             y = y + res.to(dt) * rs.to(dt).view(N, 1, 1, 1, -1) + rb.to(dt).view(N, 1, 1, 1, -1)
         if recipe['tanh']:
             y = torch.tanh(y)
+        err = {}
         if recipe['out_f32']:
-            assert rel_l2(out, y) < 1e-4, 'forward (f32 output) rel %.2e' % rel_l2(out, y)
+            err['f32'] = rel_l2(out, y)
+            assert err['f32'] < tol['f32'], 'forward (f32 output) rel %.2e' % err['f32']
         else:
-            close_bf16(out, y, 'forward')
+            err['out'] = float((out.double().cpu() - y.double()).abs().max() / y.double().abs().max())
+            close_bf16(out, y, 'forward', rel=tol['rel'], floor=tol['floor'])
         if sums is not None:
-            yq = bf(y) if not recipe['out_f32'] else y
+            yq = bf(y, storage) if not recipe['out_f32'] else y
             ref_sums = torch.stack([yq.sum(dim=(1, 2, 3)), (yq ** 2).sum(dim=(1, 2, 3))], dim=-1)
-            assert rel_l2(sums.sum(0), ref_sums) < 2e-2, 'IN statistics'
-        return
+            err['sums'] = rel_l2(sums.sum(0), ref_sums)
+            assert err['sums'] < tol['sums'], 'IN statistics rel %.2e' % err['sums']
+        return err
     odims = lay.out_dims
     dy = torch.randn(recipe['src']['N'] if kind == 'wgrad' else recipe['N'], *odims, L['cout'], generator=g)
     dys = dy if recipe['dy_f32'] else dy.to(torch.bfloat16)

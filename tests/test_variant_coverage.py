@@ -1,4 +1,5 @@
-"""CPU: every kernel variant that BASELINE configs 2, 3 and 4 run has a parity case on the GPU (tests/test_gpu_layers.py).
+"""CPU: every kernel variant that BASELINE configs 2, 3 and 4 run has a parity case on the GPU (tests/test_gpu_layers.py), and so has
+every variant of the sliding-window inference forward, on the bf16 and on the fp16 library (tests/test_gpu_infer_layers.py).
 
 The kernels pick a template instantiation per launch (channel panel, voxel tile, weights in LDS or L2, fused / class-parallel
 output-parity classes, single-channel staging, the 32x32x16 flavour, weight-gradient slab shapes ...), and the choice depends
@@ -6,7 +7,9 @@ on the problem size -- so a parity suite made of small hand-picked shapes can be
 times are never compared with the oracle.  Here the real schedules are walked in dry-run mode (tests/layer_recipes.py) and
 the variant of every convolution launch is collected through vg_conv3d_variant / vg_conv3d_wgrad_variant."""
 import pytest
+import torch
 
+import call_recipes as CR
 import layer_recipes as LR
 
 
@@ -38,6 +41,95 @@ def test_every_variant_of_the_baseline_configs_has_a_gpu_parity_case():
                  'bs2,pl>',
                  'conv_dma<128,256>', 'conv_dma<64,256>', '|gt8|', '|gt9|', 'ks1|cls0', 'ks0|cls1', 'cls1|walk1'):
         assert frag in names, frag
+
+
+# what only the sliding-window inference forward (two 128^3 windows per batch) selects: no train step of BASELINE configs 1-4 launches these
+INFERENCE_ONLY = {
+    'conv_thin2<m1,b1,r1,s1>|walk1|ch1',                            # enc1.cb2, dec1.cb2
+    'conv_thin2<m1,b1,r0,s1>|walk1|ch1',                            # dec1.cb1
+    'conv<bf16,64,2,n0,wl0,dma0,mc0,c10>|walk1|ch0|ks1',            # enc2.cb1
+    'conv32<128,1,n0,cp0>|walk0|ch1',                               # enc3.cb1, enc3.cb2, dec3.short, dec3.cb1, dec3.cb2
+    'conv<bf16,32,1,n0,wl1,dma0,mc0,c10>|walk0|ch1|ks1',            # enc4.short
+    'conv<bf16,32,1,n0,wl0,dma0,mc0,c10>|walk0|ch1|ks4',            # enc4.cb1, enc4.cb2, bridge.cb1, bridge.cb2: the K-split exchange
+}
+
+
+def test_every_variant_of_the_inference_forward_has_a_gpu_parity_case():
+    """The published inference line (bench.py --infer) runs ResUNet.forward(save=False) on 128^3 windows, two per batch (one in the tail
+    batch of an odd window count).  Its launches are walked like the train steps'; every variant has a representative that
+    tests/test_gpu_infer_layers.py replays (the inference-only ones on the bf16 library, all of them on the fp16 library), and the set of
+    inference-only variants is pinned BY NAME: a dispatch change that moves the inference path onto other kernels fails here."""
+    walks = LR.all_inference_walks()
+    for cfg in LR.INFER_NEEDED:
+        recs = walks[cfg][0]
+        assert [k for k, _, _, _ in recs] == ['fwd'] * 29, cfg              # 29 convolution launches, no other kind
+        assert [n for n, _ in walks[cfg][1]] == ['vg_stem_short_fwd']       # and the stem shortcut as an affine function of the volume
+    reps, needed = LR.inference_representatives(), LR.inference_needed_variants()
+    missing = [kv for kv in needed if kv not in reps]
+    assert not missing, missing
+    for kv in needed:
+        r = reps[kv]
+        assert r['recipe']['kind'] == 'fwd' and (r['config'] in LR.INFER_CONFIGS or r['config'] in LR.CONFIGS)
+        assert r['macs'] <= max(x['macs'] for x in LR.representatives().values())          # no case heavier than test_gpu_layers.py's heaviest
+        assert LR.recipe_variant(r['recipe']) == kv[1], kv                  # a shrunk representative still selects the identical variant
+    new = {v for _, v in LR.inference_only_variants()}
+    assert new == INFERENCE_ONLY, (sorted(new - INFERENCE_ONLY), sorted(INFERENCE_ONLY - new))
+    assert not {v for k, _, v, _ in walks['infer 128^3 N1'][0]} & INFERENCE_ONLY          # all of them come from the two-window batch
+
+
+@pytest.mark.parametrize('cfg', LR.INFER_NEEDED)
+def test_fp16_network_selects_the_same_variants(cfg):
+    """The dispatch is host logic shared by libvangan_hip.so and libvangan_hip_h.so: a torch.float16 network walks the same variant strings."""
+    dims, N = LR.INFER_CONFIGS[cfg]
+    h = LR.walk_inference(dims, N, torch.float16)
+    assert [(k, n, v) for k, n, v, _ in h[0]] == [(k, n, v) for k, n, v, _ in LR.all_inference_walks()[cfg][0]]
+    assert h[1] == LR.all_inference_walks()[cfg][1]
+
+
+def test_every_finalisation_tail_of_the_inference_forward_has_a_gpu_case():
+    """The out_jobs of ResUNet._block_fwd: each (forward variant, tail job shape) of the inference walks is already one of the train steps'
+    (call_recipes.needed_fin, replayed by tests/test_gpu_calls.py) or has a run_fin case in tests/test_gpu_infer_layers.py."""
+    have = set(CR.needed_fin())
+    cov = {c['covers'][0][1:] for c in CR.inference_fin_cases().values()}
+    need = CR.inference_needed_fin()
+    assert len(need) >= 20
+    missing = [k for k in need if k not in have and k not in cov]
+    assert not missing, missing
+    assert {v for v, _ in cov} == INFERENCE_ONLY and not cov & have       # exactly the inference-only variants carry new tails
+    for c in CR.inference_fin_cases().values():
+        r = c['recipe']
+        assert LR.recipe_variant(r) == c['variant'] and CR.fin_shape(r) == c['covers'][0][2]
+        assert r['fin']['count'] * r['layer']['stride'] ** 3 == float(torch.tensor(r['src']['dims']).prod())
+
+
+def test_fp16_bound_holds_for_the_reference_alone():
+    """The fp16 bounds of layer_recipes.FWD_TOL are the bf16 ones scaled by 2^-3 (11 significand bits against 8), not measured on the
+    kernels.  Here the reference itself is held to them: a float32 convolution of the fp16-rounded operands followed by .half() -- what a
+    correct kernel computes, up to accumulation order -- against the float64 restatement, on the 32^3 walk's enc2.cb1 call (32 -> 64
+    channels, stride 2, on-read InstanceNorm + ReLU, 864-term sums).  No element may fall outside."""
+    from oracle import vangan_oracle as O
+    recipe = next(r for _, n, _, r in LR.all_inference_walks()['infer 32^3 N2'][0] if n == 'enc2.cb1.conv')
+    L, sr, st16 = recipe['layer'], recipe['src'], torch.float16
+    g = torch.Generator().manual_seed(1)
+    st, _ = LR.make_layer_from(L, 'cpu', dtype=st16)
+    _, host = LR.make_operand(sr, L['pad'], 'cpu', g, st16)
+    tol = LR.FWD_TOL[st16]
+    assert tol == dict(rel=LR.FWD_TOL[torch.bfloat16]['rel'] / 8, floor=LR.FWD_TOL[torch.bfloat16]['floor'] / 8,
+                       sums=LR.FWD_TOL[torch.bfloat16]['sums'] / 8, f32=1e-4)
+    ys = {}
+    for dt in (torch.float64, torch.float32):
+        ap = LR.ref_operand(sr, host, L['pad'], dt, st16)
+        assert torch.equal(ap, ap.half().to(dt))                          # operands are fp16 values in both
+        w = LR.bf(st.param('c.w').to(dt), st16)
+        ys[dt] = O.to_ndhwc(O.conv3d(ap, w, st.param('c.b').to(dt), L['stride'], 'valid'))
+    got, ref = ys[torch.float32].half(), ys[torch.float64]
+    assert got.shape == (sr['N'], 8, 8, 8, 64) and float(ref.abs().max()) > 1.0
+    LR.close_bf16(got, ref, 'float32 reference + .half()', rel=tol['rel'], floor=tol['floor'])
+    sums = lambda y: torch.stack([y.sum(dim=(1, 2, 3)), (y ** 2).sum(dim=(1, 2, 3))], dim=-1)
+    assert LR.rel_l2(sums(got.float()), sums(LR.bf(ref, st16))) < tol['sums']
+    # and the bound is not vacuous: the same result rounded to bf16 instead is far outside it
+    with pytest.raises(AssertionError):
+        LR.close_bf16(ys[torch.float32].bfloat16(), ref, 'bf16 rounding', rel=tol['rel'], floor=tol['floor'])
 
 
 def test_resnet_generator_walk():
