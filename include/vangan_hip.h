@@ -656,6 +656,44 @@ int vg_clip_rescale(const float* z, int64_t n, const float* stats4, double f_lo,
 int vg_resample_axis(const float* x, int64_t outer, int L, int64_t inner, int T, const int32_t* first, const float* w8, float* out,
                      vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Label-volume preprocessing (the partition 'S' branch of process_tiff, preprocessing.py:173-189: min_max_norm, inversion when
+ * scipy.stats.mode of the normalised stack is 1, (x - 0.5) / 0.5, binarise), restated; van_gan_amd/preprocess.py (value_mode,
+ * prepare_segmentation), csrc/vg_labelprep.hip, DESIGN.md section 3.14.  fp32, the same code in both storage builds.  Every entry only
+ * enqueues, allocates nothing, reads nothing back and checks its arguments on the host before any launch (VG_EINVAL, nothing launched):
+ * a NULL pointer (mm4_or_null excepted), n < 1 or n >= 2^31, a pointer that is not 4-byte aligned, a scratch smaller than its query says
+ * or not 16-byte aligned.  Only integer atomics, and every reduction is an integer sum or maximum: equal inputs give bit-identical
+ * results on every run, whatever slot of the table a value lands in.  Every probe loop is bounded by the slot count of its table, and no
+ * workgroup waits on another.
+ *
+ * vg_value_mode: the exact mode of the n values of x -- the most frequent value, and among equally frequent values the numerically
+ *   smallest (scipy.stats.mode(x, axis=None)); -0.0 and +0.0 are one value, reported as +0.0.  mm4_or_null != NULL: the row
+ *   (min, max, ., .) vg_minmax wrote, on the device; the values counted are then y = (x - min) / (max - min), formed on the fly in fp32
+ *   with each of the three operations rounded (no reciprocal, no contraction) -- the normalisation is not injective in fp32, so the mode
+ *   of y is not the image of the mode of x.  result4 (device): [0] the mode's fp32 bits, [1] its count, [2] status -- 0 ok, bit 0 the
+ *   table overflowed (cannot happen with the scratch the query asks for), bit 1 max > min does not hold while normalising -- [3] the
+ *   number of non-finite values met, which are counted here and never inserted; when no value is finite, [0] is a NaN and [1] is 0.
+ *   n < 2^31: 32-bit counts cannot overflow.  scratch: vg_value_mode_scratch_bytes(n) bytes, 16-byte aligned, contents irrelevant on
+ *   entry: a 64-byte header and an open-addressing table of 2^k >= 2 n slots of (32-bit key, 32-bit count), the empty key a NaN pattern.
+ *   Four launches whatever the data: fill the table; count -- 0 and 1 in registers, one atomic each per workgroup; every other value
+ *   through a combiner of VG_MODE_LDS_SLOTS slots in LDS that is flushed with one global insert per occupied slot, a value that finds
+ *   the combiner full going to the table directly; 16-byte loads when x is 16-byte aligned --; a 64-bit integer maximum of
+ *   (count << 32 | inverted order key) over the table; one thread that folds in the counts of 0 and 1 and writes result4.
+ * vg_label_finish: y = (x - min) / (max - min) from mm4; when result4 says the mode is 1.0 with status 0, y = |y - 1|; z = (y - 0.5) / 0.5;
+ *   out = z < 0 ? -1 : +1 -- fp32, each operation rounded.  Every thread reads the decision from result4 on the device.  out may be x.
+ *   state: 8 words on the device; [0] is left alone (the caller's non-finite counter), [1] 1 when inverted else 0, [2], [3] the bits of
+ *   (min, max), [4..7] a copy of result4 -- what one optional read-back needs.  When min == max the output is unspecified (the kernel still
+ *   terminates and writes only inside out and state).
+ * The clamp to [0, 255] the reference applies to a resized label stack is vg_clip_rescale with stats4 = (0, 0, 255, 255), fractions 0 and
+ * rescale = 0.
+ * --------------------------------------------------------------------------------------------- */
+#define VG_MODE_LDS_SLOTS 1024
+int64_t vg_value_mode_scratch_bytes(int64_t n);
+int vg_value_mode(const float* x, int64_t n, const float* mm4_or_null, uint32_t* result4, void* scratch, int64_t scratch_bytes,
+                  vg_stream_t stream);
+int vg_label_finish(const float* x, int64_t n, const float* mm4, const uint32_t* result4, float* out, uint32_t* state,
+                    vg_stream_t stream);
+
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */
 int vg_memset_zero(void* p, int64_t nbytes, vg_stream_t stream);

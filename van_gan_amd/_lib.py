@@ -141,6 +141,9 @@ _SIGS = {
     'vg_order_stats': ([c_void_p, c_i64, C.POINTER(c_i64), c_int, c_void_p, c_void_p, c_i64, c_void_p], c_int),
     'vg_clip_rescale': ([c_void_p, c_i64, c_void_p, C.c_double, C.c_double, c_int, c_void_p, c_void_p, c_void_p], c_int),
     'vg_resample_axis': ([c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_value_mode_scratch_bytes': ([c_i64], c_i64),
+    'vg_value_mode': ([c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p], c_int),
+    'vg_label_finish': ([c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

@@ -61,6 +61,16 @@ class DataPipeline:
         self._order_i: List[int] = []
         self._order_s: List[int] = []
 
+    @classmethod
+    def from_raw(cls, imaging_raw: Sequence, segmentation_raw: Sequence, patch: Tuple[int, int, int], batch_size: int, seed: int = 0,
+                 otf_imaging: bool = True, imaging_kw: Optional[dict] = None, segmentation_kw: Optional[dict] = None) -> 'DataPipeline':
+        """The pipeline over raw stacks (whatever preprocess.as_raw_volume takes): every imaging stack goes through prepare_imaging(**imaging_kw)
+        and every label stack through prepare_segmentation(**segmentation_kw) on the device, as process_tiff prepares the two partitions."""
+        from .preprocess import prepare_imaging, prepare_segmentation
+        imaging = [prepare_imaging(r, **(imaging_kw or {})) for r in imaging_raw]
+        segmentation = [prepare_segmentation(r, **(segmentation_kw or {})) for r in segmentation_raw]
+        return cls(imaging, segmentation, patch, batch_size, seed=seed, otf_imaging=otf_imaging)
+
     # -- draws (host): the reference shuffles the file lists once per pass (dataset.py:137-190) --
     def _next(self, order: List[int], n: int) -> int:
         if not order:

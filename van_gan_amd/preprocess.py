@@ -1,9 +1,10 @@
 """Raw-volume preprocessing on MI355X: the imaging-domain recipe the reference runs before run_mapping (main.py:255-270) --
 preprocess_rsom_images (main.py:127-150: z-score every z-slice, clip to two percentiles of the whole volume with
 scipy.stats.scoreatpercentile) followed by process_tiff's min_max_norm and (x - 0.5) / 0.5 and its NaN check (preprocessing.py:179-215)
--- and, on request, process_tiff's resize_volume between the two (utils.py:224-255: Lanczos-4) -- without the TIFF I/O and the label-domain
-branch.  The arithmetic runs in csrc/vg_preproc.hip and csrc/vg_resample.hip (include/vangan_hip.h "Raw-volume
-preprocessing" and "Volume resize", DESIGN.md sections 3.12 and 3.13); this module owns buffers, ranks, filter tables and checks.
+-- and, on request, process_tiff's resize_volume between the two (utils.py:224-255: Lanczos-4) -- and process_tiff's label-domain branch
+(preprocessing.py:173-189: prepare_segmentation), without the TIFF I/O.  The arithmetic runs in csrc/vg_preproc.hip,
+csrc/vg_resample.hip and csrc/vg_labelprep.hip (include/vangan_hip.h "Raw-volume preprocessing", "Volume resize" and "Label-volume
+preprocessing", DESIGN.md sections 3.12 to 3.14); this module owns buffers, ranks, filter tables and checks.
 
 A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost -- process_tiff's layout after its transpose -- as uint8, uint16 or float32, a numpy
 array or a torch tensor, on the host or on the device.  torch has no uint16 arithmetic, so a 16-bit stack travels as the int16 tensor of
@@ -24,6 +25,7 @@ from .ops import _p, stream
 
 PP_U8, PP_U16, PP_F32 = 0, 1, 2            # VG_PP_U8, VG_PP_U16, VG_PP_F32
 MAX_RANKS = 4                              # VG_PP_MAX_RANKS
+MODE_LDS_SLOTS = 1024                      # VG_MODE_LDS_SLOTS: the slots of value_mode's per-workgroup combiner
 MINMAX_ERROR = 'Cannot perform min-max normalization when max and min are equal.'       # the message of min_max_norm (utils.py:23)
 _T_UINT16 = getattr(torch, 'uint16', None)
 
@@ -411,3 +413,85 @@ def prepare_imaging(raw, preprocess: Optional[str] = 'rsom', lower_thresh: float
             if float(lims[0]) == float(lims[1]):
                 raise ValueError(MINMAX_ERROR)
     return out[..., None]
+
+
+# ------------------------------------------------------------------------------------------------ label volumes
+def _value_mode_into(x: torch.Tensor, mm_ptr, result: torch.Tensor) -> None:
+    """result (4 int32 words on the device) = vg_value_mode of x, of its min-max normalisation when mm_ptr names a vg_minmax row."""
+    n = x.numel()
+    nbytes = int(lib.vg_value_mode_scratch_bytes(n))
+    _check(nbytes, 'vg_value_mode_scratch_bytes')
+    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
+    _check(lib.vg_value_mode(_p(x), n, mm_ptr, _p(result), _p(scratch), nbytes, stream()), 'vg_value_mode')
+
+
+def _mode_count_ok(n: int, what: str) -> None:
+    if n < 1 or n >= 2 ** 31:
+        raise ValueError('%s serves 1 <= n < 2^31 elements, got %d' % (what, n))
+
+
+def value_mode(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(value, count): the most frequent value of x as a one-element fp32 device tensor and how often it occurs as a one-element int32
+    device tensor -- scipy.stats.mode(x, axis=None): among equally frequent values the smallest; -0.0 and +0.0 are one value.  Exact.
+    x: fp32 on the device, fewer than 2^31 elements; non-finite values are not counted (all non-finite: a NaN with count 0).
+    Enqueue-only: four launches, no sort and no read-back; the hash table it counts in takes 16 to 32 bytes of scratch per element."""
+    x = _dev_f32(x)
+    _mode_count_ok(x.numel(), 'value_mode')
+    with torch.cuda.device(x.device):
+        result = torch.empty(4, dtype=torch.int32, device=x.device)
+        _value_mode_into(x, None, result)
+    return result[0:1].view(torch.float32), result[1:2]
+
+
+@functools.lru_cache(maxsize=8)
+def _label_clamp_stats(dev: torch.device) -> torch.Tensor:
+    """(0, 0, 255, 255) on the device, kept per device: vg_clip_rescale's order statistics for the clamp of a resized label stack."""
+    return torch.tensor([0.0, 0.0, 255.0, 255.0], dtype=torch.float32).to(dev)
+
+
+def prepare_segmentation(raw, check: bool = True, device=None, target_size=None, return_info: bool = False):
+    """Raw label volume -> what DataPipeline takes as a segmentation volume: fp32 [X,Y,Z,1] in {-1, +1} on the device -- process_tiff's
+    partition 'S' branch (preprocessing.py:173-189): min_max_norm; when the most frequent value of the normalised stack is 1 (the
+    background is the bright level) the stack is inverted, |y - 1|; (y - 0.5) / 0.5; negative -> -1, else +1.  Every step in fp32 as numpy
+    rounds it; the mode is exact (value_mode's table, counting the normalised values: the normalisation can merge neighbouring values).
+    raw: whatever as_raw_volume takes.  target_size=(T0, T1, T2): process_tiff's resize=True -- resize_volume, then the clamp to [0, 255]
+    the reference applies to a resized label stack, then the above; a target equal to the volume's shape is skipped, clamp included.
+    check=True reads one small block back and raises ValueError('NaN detected') when the raw volume holds a non-finite value,
+    min_max_norm's ValueError when the two limits coincide, and RuntimeError on a non-zero status word of the mode.  check=False reads
+    nothing back: the call only enqueues, and the launches it makes do not depend on the data.  return_info=True: (out, dict(inverted,
+    mode, count, min, max)) -- the mode of the normalised stack and its count, the limits of the stack; this needs the read-back.
+    Temporary device memory: the fp32 volume and the mode's table of 16 to 32 bytes per voxel (1 GiB at 512x512x140)."""
+    tgt = None if target_size is None else _target3(target_size)
+    v = as_raw_volume(raw, device)
+    if tgt == tuple(v.shape):
+        tgt = None
+    _mode_count_ok(math.prod(v.shape if tgt is None else tgt), 'prepare_segmentation')
+    dev = v.buf.device
+    with torch.cuda.device(dev):
+        state = torch.zeros(8, dtype=torch.int32, device=dev)       # [0] non-finite counter, [1..7] written by vg_label_finish
+        x = _to_f32(v, _p(state))                                   # ours: everything below runs in place
+        if tgt is not None:
+            x = _resize_f32(x, tgt)
+            n = x.numel()
+            _check(lib.vg_clip_rescale(_p(x), n, _p(_label_clamp_stats(dev)), 0.0, 0.0, 0, _p(state) + 8, _p(x), stream()), 'vg_clip_rescale')
+        n = x.numel()
+        mm = torch.zeros(1, 4, device=dev)
+        _check(lib.vg_minmax(_p(x), 1, n, _p(mm), stream()), 'vg_minmax')
+        result = torch.empty(4, dtype=torch.int32, device=dev)
+        _value_mode_into(x, _p(mm), result)
+        _check(lib.vg_label_finish(_p(x), n, _p(mm), _p(result), _p(x), _p(state), stream()), 'vg_label_finish')
+        info = None
+        if check or return_info:
+            host = state.cpu()
+            lims = host[2:4].view(torch.float32)
+            if check:
+                if int(host[0]) != 0:
+                    raise ValueError('NaN detected')
+                if float(lims[0]) == float(lims[1]):
+                    raise ValueError(MINMAX_ERROR)
+                if int(host[6]) != 0:
+                    raise RuntimeError('vg_value_mode reported status %d' % int(host[6]))
+            info = dict(inverted=bool(int(host[1])), mode=float(host[4:5].view(torch.float32)[0]), count=int(host[5]),
+                        min=float(lims[0]), max=float(lims[1]))
+    out = x[..., None]
+    return (out, info) if return_info else out
