@@ -694,6 +694,41 @@ int vg_value_mode(const float* x, int64_t n, const float* mm4_or_null, uint32_t*
 int vg_label_finish(const float* x, int64_t n, const float* mm4, const uint32_t* result4, float* out, uint32_t* state,
                     vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Imaging filters (scipy.ndimage.median_filter and threshold_outliers, utils.py:108-133, both brought in by the reference's driver,
+ * main.py:34-36), restated; van_gan_amd/preprocess.py (median_filter, volume_moments, outlier_limits, threshold_outliers),
+ * csrc/vg_filters.hip, DESIGN.md section 3.15.  The same code in both storage builds.  vol: [X][Y][Z] with Z innermost, n = X * Y * Z;
+ * dtype is one of VG_PP_U8 / VG_PP_U16 / VG_PP_F32 and the values are converted to fp32 exactly.  Every entry only enqueues, allocates
+ * nothing and checks its arguments on the host before any launch (VG_EINVAL, nothing launched): NULL pointers, an unknown dtype, a
+ * pointer that is not aligned for its type, a scratch smaller than its query says, and what is listed per entry.  Only integer atomics:
+ * equal inputs give bit-identical results on every run.  No result depends on what an output or scratch buffer held before, the
+ * non-finite counters excepted, which are ADDED to and zeroed by the caller (as vg_zscore_slices' is).
+ *
+ * vg_median3: out[x][y][z] = the value of rank m / 2 (0-based) among the m = sx * sy * sz values of the window centred on the voxel;
+ *   each of sx, sy, sz is 1 (no neighbours along that axis) or 3, anything else is VG_EINVAL.  (3,3,3) is the 3-D median, (3,3,1) the
+ *   median of every z-slice.  The boundary is scipy's default mode='reflect': index -1 reads index 0 and index n reads index n - 1, so an
+ *   axis of length 1 reads its only element three times.  The result is one of the inputs, hence exact.  *nonfinite has the number of
+ *   non-finite voxels of vol ADDED to it (each counted once, at its own position); where a window holds a NaN the output value is
+ *   unspecified (scipy's is order-dependent there).  X, Y >= 1, X * Y < 2^40, 1 <= Z <= 2^20; out (n floats) must not overlap vol.
+ * vg_volume_moments: mean_std[0..1] = (mean, population standard deviation) of the n values, accumulated as vg_slice_moments does: fp64
+ *   sums of (x - vol[0]) and of its square (a constant volume gives exactly 0) per workgroup into the caller's scratch
+ *   (vg_volume_moments_scratch_bytes(n) bytes, 16-byte aligned), summed in a fixed order by a second kernel, rounded once to fp32.
+ *   1 <= n < 2^60.
+ * vg_outlier_limits: with (m, s) = mean_std read on the device, a voxel is kept when fabsf((x - m) / s) <= threshold in fp32, every
+ *   operation rounded and the division correctly rounded; a NaN compares false, so a NaN voxel is never kept and no voxel is when s is 0
+ *   or not finite.  stats4 = (lo, lo, hi, hi), lo / hi the smallest / largest kept value -- taken by integer atomic min / max on the
+ *   order-preserving key of vg_order_stats, held in stats4 itself meanwhile, and converted by a last one-thread kernel -- laid out for
+ *   vg_clip_rescale with fractions 0.  kept_nonfinite2[0] = the number of kept voxels, saturating at 2^32 - 1; kept_nonfinite2[1] has the
+ *   number of non-finite voxels ADDED to it.  No kept voxel: stats4 = (+inf, +inf, -inf, -inf).  threshold must be finite and > 0;
+ *   1 <= n < 2^60.  Three launches whatever the data.
+ * --------------------------------------------------------------------------------------------- */
+int vg_median3(const void* vol, int dtype, int X, int Y, int Z, int sx, int sy, int sz, float* out, uint32_t* nonfinite,
+               vg_stream_t stream);
+int64_t vg_volume_moments_scratch_bytes(int64_t n);
+int vg_volume_moments(const void* vol, int dtype, int64_t n, float* mean_std, void* scratch, int64_t scratch_bytes, vg_stream_t stream);
+int vg_outlier_limits(const void* vol, int dtype, int64_t n, const float* mean_std, float threshold, float* stats4,
+                      uint32_t* kept_nonfinite2, vg_stream_t stream);
+
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */
 int vg_memset_zero(void* p, int64_t nbytes, vg_stream_t stream);

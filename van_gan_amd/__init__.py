@@ -6,5 +6,6 @@ Python.  Importing it builds/loads ``libvangan_hip.so`` (hand-written gfx950 HIP
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library cannot be built/loaded)
 from .vangan import NETS, RESULT_KEYS, VanGan  # noqa: F401
-from .preprocess import (lanczos4_table, order_stats, percentiles, prepare_imaging, prepare_segmentation,  # noqa: F401
-                         preprocess_rsom_images, resize_volume, slice_moments, value_mode, zscore_slices)
+from .preprocess import (lanczos4_table, median_filter, order_stats, outlier_limits, percentiles, prepare_imaging,  # noqa: F401
+                         prepare_segmentation, preprocess_rsom_images, resize_volume, slice_moments, threshold_outliers, value_mode,
+                         volume_moments, zscore_slices)

@@ -144,6 +144,10 @@ _SIGS = {
     'vg_value_mode_scratch_bytes': ([c_i64], c_i64),
     'vg_value_mode': ([c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p], c_int),
     'vg_label_finish': ([c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_median3': ([c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p], c_int),
+    'vg_volume_moments_scratch_bytes': ([c_i64], c_i64),
+    'vg_volume_moments': ([c_void_p, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p], c_int),
+    'vg_outlier_limits': ([c_void_p, c_int, c_i64, c_void_p, c_float, c_void_p, c_void_p, c_void_p], c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

@@ -2,9 +2,11 @@
 preprocess_rsom_images (main.py:127-150: z-score every z-slice, clip to two percentiles of the whole volume with
 scipy.stats.scoreatpercentile) followed by process_tiff's min_max_norm and (x - 0.5) / 0.5 and its NaN check (preprocessing.py:179-215)
 -- and, on request, process_tiff's resize_volume between the two (utils.py:224-255: Lanczos-4) -- and process_tiff's label-domain branch
-(preprocessing.py:173-189: prepare_segmentation), without the TIFF I/O.  The arithmetic runs in csrc/vg_preproc.hip,
-csrc/vg_resample.hip and csrc/vg_labelprep.hip (include/vangan_hip.h "Raw-volume preprocessing", "Volume resize" and "Label-volume
-preprocessing", DESIGN.md sections 3.12 to 3.14); this module owns buffers, ranks, filter tables and checks.
+(preprocessing.py:173-189: prepare_segmentation), without the TIFF I/O -- and the two further preprocessors the
+reference's driver brings in for imaging volumes, scipy.ndimage.median_filter and threshold_outliers (main.py:34-36, utils.py:108-133),
+as functions of their own and as stages of prepare_imaging.  The arithmetic runs in csrc/vg_preproc.hip, csrc/vg_resample.hip,
+csrc/vg_labelprep.hip and csrc/vg_filters.hip (include/vangan_hip.h "Raw-volume preprocessing", "Volume resize", "Label-volume
+preprocessing" and "Imaging filters", DESIGN.md sections 3.12 to 3.15); this module owns buffers, ranks, filter tables and checks.
 
 A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost -- process_tiff's layout after its transpose -- as uint8, uint16 or float32, a numpy
 array or a torch tensor, on the host or on the device.  torch has no uint16 arithmetic, so a 16-bit stack travels as the int16 tensor of
@@ -204,9 +206,10 @@ def _clip_into(z: torch.Tensor, lower_thresh: float, upper_thresh: float, rescal
     _check(lib.vg_clip_rescale(_p(z), n, _p(stats), lo[2], hi[2], 1 if rescale else 0, limits_ptr, _p(out), stream()), 'vg_clip_rescale')
 
 
-def _state_block(dev) -> torch.Tensor:
-    """Four 32-bit words read back in one copy: [0] the non-finite counter, [2], [3] the fp32 limits (lp, up)."""
-    return torch.zeros(4, dtype=torch.int32, device=dev)
+def _state_block(dev, words: int = 4) -> torch.Tensor:
+    """32-bit words read back in one copy: [0] the non-finite counter, [2], [3] the fp32 limits (lp, up); with words=8 also [4], [5] the
+    kept and the non-finite count of an 'outliers' stage."""
+    return torch.zeros(words, dtype=torch.int32, device=dev)
 
 
 def preprocess_rsom_images(vol, lower_thresh: float = 0.05, upper_thresh: float = 99.95, device=None) -> torch.Tensor:
@@ -373,43 +376,187 @@ def _minmax_rescale(x: torch.Tensor, limits_ptr: int) -> None:
     _check(lib.vg_clip_rescale(_p(x), n, _p(stats), 0.0, 0.0, 1, limits_ptr, _p(x), stream()), 'vg_clip_rescale')
 
 
-def prepare_imaging(raw, preprocess: Optional[str] = 'rsom', lower_thresh: float = 0.05, upper_thresh: float = 99.95, check: bool = True,
-                    device=None, target_size=None) -> torch.Tensor:
+# ------------------------------------------------------------------------------------------------ imaging filters
+# scipy.ndimage.median_filter (main.py:36) and threshold_outliers (utils.py:108-133, main.py:34): csrc/vg_filters.hip, include/vangan_hip.h
+# "Imaging filters", DESIGN.md section 3.15.
+STAGES = ('median', 'outliers', 'rsom')
+OUTLIERS_ERROR = 'threshold_outliers: no voxel lies within the threshold'
+
+
+def _median_size3(size) -> Tuple[int, int, int]:
+    """(sx, sy, sz), each 1 or 3, from an int (the same along every axis) or a 3-tuple: what vg_median3 serves."""
+    try:
+        s3 = (operator.index(size),) * 3
+    except TypeError:
+        try:
+            s3 = tuple(operator.index(s) for s in size)
+        except TypeError:
+            raise ValueError('a median size is an int or three ints, got %r' % (size,)) from None
+    if len(s3) != 3 or any(s not in (1, 3) for s in s3):
+        raise ValueError('the median filter serves sizes of 1 or 3 along each of three axes, got %r' % (size,))
+    return s3
+
+
+def _outlier_threshold(threshold) -> float:
+    try:
+        thr = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError('the outlier threshold is a number, got %r' % (threshold,)) from None
+    if not (math.isfinite(thr) and thr > 0.0 and math.isfinite(float(np.float32(thr))) and float(np.float32(thr)) > 0.0):
+        raise ValueError('the outlier threshold must be finite and > 0, got %r' % (threshold,))
+    return thr
+
+
+def _median_into(v: RawVolume, size3: Tuple[int, int, int], counter_ptr: int) -> torch.Tensor:
+    X, Y, Z = v.shape
+    out = torch.empty(v.shape, device=v.buf.device)
+    _check(lib.vg_median3(_p(v.buf), v.code, X, Y, Z, size3[0], size3[1], size3[2], _p(out), counter_ptr, stream()), 'vg_median3')
+    return out
+
+
+def _volume_moments_into(v: RawVolume, ms: torch.Tensor) -> None:
+    nbytes = int(lib.vg_volume_moments_scratch_bytes(v.numel))
+    _check(nbytes, 'vg_volume_moments_scratch_bytes')
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=v.buf.device)
+    _check(lib.vg_volume_moments(_p(v.buf), v.code, v.numel, _p(ms), _p(scratch), nbytes, stream()), 'vg_volume_moments')
+
+
+def _outlier_limits_into(v: RawVolume, threshold: float, stats: torch.Tensor, counts_ptr: int) -> None:
+    """stats (4 fp32 on the device) = (lo, lo, hi, hi) of v; counts_ptr names (kept, non-finite): the second word is added to."""
+    ms = torch.empty(2, device=v.buf.device)
+    _volume_moments_into(v, ms)
+    _check(lib.vg_outlier_limits(_p(v.buf), v.code, v.numel, _p(ms), threshold, _p(stats), counts_ptr, stream()), 'vg_outlier_limits')
+
+
+def _outliers_into(v: RawVolume, threshold: float, rescale: bool, state: torch.Tensor) -> torch.Tensor:
+    """threshold_outliers of v as a new fp32 tensor (optionally with the rescale to [-1, 1]); state: the 8-word block of prepare_imaging."""
+    stats = torch.empty(4, device=v.buf.device)
+    _outlier_limits_into(v, threshold, stats, _p(state) + 16)
+    if v.code == PP_F32:
+        x, out = v.buf.view(v.shape), torch.empty(v.shape, device=v.buf.device)
+    else:
+        x = out = _to_f32(v, _p(state))
+    _check(lib.vg_clip_rescale(_p(x), v.numel, _p(stats), 0.0, 0.0, 1 if rescale else 0, _p(state) + 8, _p(out), stream()), 'vg_clip_rescale')
+    return out
+
+
+def median_filter(vol, size=3, device=None, return_count: bool = False):
+    """scipy.ndimage.median_filter(vol, size=size) with its default mode='reflect', on the device: fp32 [X,Y,Z], exact (a median is one of
+    the values).  size: an int or (sx, sy, sz), each 1 or 3 -- 3 is the 3-D median, (3, 3, 1) the median of every z-slice; anything else
+    raises ValueError before the device is touched.  return_count: also the one-element int32 device tensor that counts the non-finite
+    voxels of vol; where a window holds a NaN the value is unspecified.  Enqueue-only."""
+    size3 = _median_size3(size)
+    v = as_raw_volume(vol, device)
+    dev = v.buf.device
+    with torch.cuda.device(dev):
+        counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        out = _median_into(v, size3, _p(counter))
+    return (out, counter) if return_count else out
+
+
+def volume_moments(vol, device=None) -> torch.Tensor:
+    """[2] fp32 on the device: (mean, population standard deviation) of the whole volume, accumulated in fp64 and rounded once."""
+    v = as_raw_volume(vol, device)
+    with torch.cuda.device(v.buf.device):
+        ms = torch.empty(2, device=v.buf.device)
+        _volume_moments_into(v, ms)
+    return ms
+
+
+def outlier_limits(vol, threshold=6, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(limits, counts) on the device: limits = (lower, upper) fp32, the smallest and the largest value x of vol with
+    |(x - mean) / std| <= threshold in fp32 (the selection of threshold_outliers, utils.py:119-128); counts = (kept, non-finite) int32,
+    kept saturating at 2^32 - 1 (read it as unsigned).  No kept voxel (a constant volume, a NaN in it): limits = (+inf, -inf).
+    Enqueue-only."""
+    thr = _outlier_threshold(threshold)
+    v = as_raw_volume(vol, device)
+    dev = v.buf.device
+    with torch.cuda.device(dev):
+        stats = torch.empty(4, device=dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        _outlier_limits_into(v, thr, stats, _p(counts))
+    return stats[1:3], counts
+
+
+def threshold_outliers(vol, threshold=6, device=None) -> torch.Tensor:
+    """threshold_outliers (utils.py:108-133) on the device: vol clipped to outlier_limits(vol, threshold); fp32 [X,Y,Z].  Moments, limits,
+    then the clip pass with those limits and no rescale.  threshold must be finite and > 0.  Enqueue-only."""
+    thr = _outlier_threshold(threshold)
+    v = as_raw_volume(vol, device)
+    dev = v.buf.device
+    with torch.cuda.device(dev):
+        return _outliers_into(v, thr, False, _state_block(dev, 8))
+
+
+def _stages(preprocess) -> Tuple[str, ...]:
+    if preprocess is None:
+        return ()
+    names = (preprocess,) if isinstance(preprocess, str) else preprocess
+    try:
+        names = tuple(names)
+    except TypeError:
+        names = (names,)
+    if not names or any(not isinstance(s, str) or s not in STAGES for s in names) or len(set(names)) != len(names):
+        raise ValueError("preprocess must be None, 'rsom', 'median', 'outliers' or a sequence of these, each at most once, got %r" % (preprocess,))
+    return names
+
+
+def prepare_imaging(raw, preprocess='rsom', lower_thresh: float = 0.05, upper_thresh: float = 99.95, check: bool = True,
+                    device=None, target_size=None, median_size=3, outlier_threshold=6) -> torch.Tensor:
     """Raw imaging volume -> what stitch_subvolumes and DataPipeline take: fp32 [X,Y,Z,1] in [-1, 1] on the device.
     preprocess='rsom': z-score per z-slice, clip to the two percentiles, min-max, (x - 0.5) / 0.5 (main.py:127-150 and
     preprocessing.py:179-185).  preprocess=None: min-max and (x - 0.5) / 0.5 alone (process_tiff without a preprocess_fn).
+    preprocess='median': median_filter(size=median_size) first; 'outliers': threshold_outliers(threshold=outlier_threshold) first.  A
+    sequence of these names, each at most once -- ('median', 'rsom'), ('outliers', 'median') -- applies the stages left to right, as one
+    composes them inside the reference's preprocess_fn; a stage that follows another reads the fp32 result of the one before it.  When the
+    last stage is a clip whose limits are on the device ('rsom', 'outliers') and there is no resize, the clip and the rescale are one
+    launch; otherwise a min / max pass and the rescale follow.
     check=True reads one small block back and raises ValueError('NaN detected') when a non-finite value was met (preprocessing.py:191-215
-    prints that and skips the file) and min_max_norm's ValueError when the two limits coincide.  check=False reads nothing back: the call
-    only enqueues, and the launches it makes do not depend on the data.
+    prints that and skips the file), ValueError('threshold_outliers: no voxel lies within the threshold') when the 'outliers' stage kept
+    nothing (numpy raises there too), and min_max_norm's ValueError when the two limits coincide.  check=False reads nothing back: the
+    call only enqueues, and the launches it makes do not depend on the data.
     target_size=(T0, T1, T2): process_tiff's resize=True (preprocessing.py:170-185) -- the preprocessed volume (clipped, not yet rescaled)
     goes through resize_volume before min_max_norm, and the result is [T0,T1,T2,1].  Lanczos-4 overshoots, so the extremes are taken from
     the resized volume by a min / max pass.  The non-finite count is that of the values before the resize.  None: no resize, today's
     launches; a target equal to the volume's shape gives the same bits as None."""
-    if preprocess not in ('rsom', None):
-        raise ValueError("preprocess must be 'rsom' or None, got %r" % (preprocess,))
+    stages = _stages(preprocess)
     percentile_rank(1, lower_thresh), percentile_rank(1, upper_thresh)
+    size3 = _median_size3(median_size)
+    thr = _outlier_threshold(outlier_threshold)
     tgt = None if target_size is None else _target3(target_size)
     v = as_raw_volume(raw, device)
     dev = v.buf.device
     with torch.cuda.device(dev):
-        state = _state_block(dev)
-        if preprocess:
-            ms = torch.empty(v.shape[2], 2, device=dev)
-            out = torch.empty(v.shape, device=dev)
-            _moments_into(v, ms)
-            _zscore_into(v, ms, out, _p(state))
-            _clip_into(out, lower_thresh, upper_thresh, tgt is None, _p(state) + 8, out)
-        else:
+        outliers = 'outliers' in stages
+        state = _state_block(dev, 8) if outliers else _state_block(dev)
+        fused = bool(stages) and stages[-1] in ('rsom', 'outliers') and tgt is None
+        out = None
+        for i, stage in enumerate(stages):
+            rescale = fused and i == len(stages) - 1
+            if stage == 'median':
+                out = _median_into(v, size3, _p(state))
+            elif stage == 'outliers':
+                out = _outliers_into(v, thr, rescale, state)
+            else:
+                ms = torch.empty(v.shape[2], 2, device=dev)
+                out = torch.empty(v.shape, device=dev)
+                _moments_into(v, ms)
+                _zscore_into(v, ms, out, _p(state))
+                _clip_into(out, lower_thresh, upper_thresh, rescale, _p(state) + 8, out)
+            v = RawVolume(out, PP_F32, v.shape)
+        if not stages:
             out = _to_f32(v, _p(state))
         if tgt is not None:
             out = _resize_f32(out, tgt)                 # `out` itself when no axis changes: ours, so the rescale below may run in place
-        if tgt is not None or not preprocess:
+        if not fused:
             _minmax_rescale(out, _p(state) + 8)
         if check:
             host = state.cpu()
-            if int(host[0]) != 0:
+            if int(host[0]) != 0 or (outliers and int(host[5]) != 0):
                 raise ValueError('NaN detected')
-            lims = host[2:].view(torch.float32)
+            if outliers and int(host[4]) == 0:
+                raise ValueError(OUTLIERS_ERROR)
+            lims = host[2:4].view(torch.float32)
             if float(lims[0]) == float(lims[1]):
                 raise ValueError(MINMAX_ERROR)
     return out[..., None]

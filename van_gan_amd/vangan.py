@@ -974,14 +974,15 @@ class VanGan:
         return _st(self, gen, img, tuple(subvol_size) if subvol_size is not None else self.dims, **kw)
 
     def segment_volume(self, gen: str, raw, subvol_size=None, *, preprocess='rsom', lower_thresh: float = 0.05, upper_thresh: float = 99.95,
-                       check: bool = True, target_size=None, **stitch_kw):
+                       check: bool = True, target_size=None, median_size=3, outlier_threshold=6, **stitch_kw):
         """Raw volume -> segmentation on the device: the reference's recipe for new images (main.py:255-270), prepare_imaging
         (van_gan_amd/preprocess.py) followed by stitch_subvolumes with the remaining keywords.  target_size=(T0, T1, T2): the raw volume is
         resized (Lanczos-4, process_new_data(resize=True)) between the preprocessing and the min-max; the result then has the target's
-        shape, as in the reference -- it is not mapped back to the raw grid."""
+        shape, as in the reference -- it is not mapped back to the raw grid.  preprocess, median_size and outlier_threshold: as in
+        prepare_imaging (the stages 'median', 'outliers' and 'rsom', alone or in a sequence)."""
         from .preprocess import prepare_imaging
         img = prepare_imaging(raw, preprocess=preprocess, lower_thresh=lower_thresh, upper_thresh=upper_thresh, check=check, device=self.device,
-                              target_size=target_size)
+                              target_size=target_size, median_size=median_size, outlier_threshold=outlier_threshold)
         return self.stitch_subvolumes(gen, img, subvol_size, **stitch_kw)
 
     # ------------------------------------------------------------------------------------------------
