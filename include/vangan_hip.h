@@ -697,7 +697,7 @@ int vg_label_finish(const float* x, int64_t n, const float* mm4, const uint32_t*
 /* ---------------------------------------------------------------------------------------------
  * Imaging filters (scipy.ndimage.median_filter and threshold_outliers, utils.py:108-133, both brought in by the reference's driver,
  * main.py:34-36), restated; van_gan_amd/preprocess.py (median_filter, volume_moments, outlier_limits, threshold_outliers),
- * csrc/vg_filters.hip, DESIGN.md section 3.15.  The same code in both storage builds.  vol: [X][Y][Z] with Z innermost, n = X * Y * Z;
+ * csrc/vg_filters.hip (vg_volume_moments: csrc/vg_preproc.hip), DESIGN.md section 3.15.  The same code in both storage builds.  vol: [X][Y][Z] with Z innermost, n = X * Y * Z;
  * dtype is one of VG_PP_U8 / VG_PP_U16 / VG_PP_F32 and the values are converted to fp32 exactly.  Every entry only enqueues, allocates
  * nothing and checks its arguments on the host before any launch (VG_EINVAL, nothing launched): NULL pointers, an unknown dtype, a
  * pointer that is not aligned for its type, a scratch smaller than its query says, and what is listed per entry.  Only integer atomics:

@@ -15,8 +15,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import filters_restate as FR  # noqa: E402
+import gpu_helpers  # noqa: E402
+from gpu_helpers import DEV, _dev, _raw, _Recorder  # noqa: E402
 
-DEV = 'cuda:0'
 F32 = np.float32
 DTYPES = ['uint8', 'uint16', 'float32']
 SIZES = [(3, 3, 3), (3, 3, 1)]
@@ -24,10 +25,6 @@ MEDIAN_SHAPES = [(1, 1, 1), (2, 2, 2), (1, 7, 4), (3, 66, 2),
                  (35, 11, 37),             # no axis a multiple of the tile (32 planes, 8 rows, 32 columns), each crosses one tile edge
                  (5, 5, 65),               # two z tiles and one column: several workgroups along the contiguous axis
                  (40, 37, 70)]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -254,14 +251,6 @@ def test_threshold_outliers_and_prepare_imaging_are_the_restatement_bitwise(dtyp
 
 
 # ------------------------------------------------------------------------------------------------ composition
-def _raw(dtype, shape=(24, 20, 35)):
-    rng = np.random.default_rng(len(dtype) + sum(shape))
-    top = 255 if dtype == 'uint8' else 65535
-    v = rng.gamma(2.0, 0.08, shape) * (1.0 + 0.3 * np.cos(np.arange(shape[2]) / 5.0))
-    v += (rng.random(shape) < 0.02) * rng.random(shape)
-    return np.clip(v * top, 0, top).astype(dtype)
-
-
 @pytest.mark.parametrize('tgt', [None, (24, 20, 32)])
 @pytest.mark.parametrize('dtype', ['uint8', 'uint16'])
 def test_stages_compose_left_to_right(dtype, tgt):
@@ -279,10 +268,7 @@ def test_stages_compose_left_to_right(dtype, tgt):
     assert torch.equal(got, prepare_imaging(median_filter(preprocess_rsom_images(raw)), preprocess=None, target_size=tgt))
 
 
-@functools.lru_cache(maxsize=None)
-def _engine():
-    from van_gan_amd import VanGan
-    return VanGan((32, 32, 32), batch_size=4, device=DEV, seed=5, precision='fp32')
+_engine = functools.lru_cache(maxsize=None)(gpu_helpers._engine)           # one engine per test module, as before
 
 
 def test_segment_volume_passes_the_stages_through(monkeypatch):
@@ -312,17 +298,6 @@ def test_segment_volume_passes_the_stages_through(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ fusion and unchanged launches
-class _Recorder:
-    """Stands in for the library handle inside van_gan_amd.preprocess and notes which entries are called."""
-
-    def __init__(self, lib):
-        self._lib, self.names = lib, []
-
-    def __getattr__(self, name):
-        self.names.append(name)
-        return getattr(self._lib, name)
-
-
 def _calls(monkeypatch, raw, **kw):
     from van_gan_amd import preprocess
     rec = _Recorder(preprocess.lib)

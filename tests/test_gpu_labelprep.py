@@ -10,13 +10,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import labelprep_restate as R  # noqa: E402
+from gpu_helpers import DEV, _dev, _Recorder  # noqa: E402
 
-DEV = 'cuda:0'
 F32 = np.float32
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _bits(words):
@@ -241,17 +237,6 @@ def test_check_raises_on_a_constant_volume_and_on_a_nan():
         out = prepare_segmentation(bad, check=False)                        # returns; whatever it holds, the device is fine afterwards
         assert isinstance(out, torch.Tensor) and out.shape == (16, 19, 7, 1)
         torch.cuda.synchronize()
-
-
-class _Recorder:
-    """Stands in for the library handle inside van_gan_amd.preprocess and notes which entries are called."""
-
-    def __init__(self, lib):
-        self._lib, self.names = lib, []
-
-    def __getattr__(self, name):
-        self.names.append(name)
-        return getattr(self._lib, name)
 
 
 def test_unchecked_call_makes_the_same_calls_whatever_the_data(monkeypatch):

@@ -11,13 +11,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import preproc_restate as P  # noqa: E402
+import gpu_helpers  # noqa: E402
+from gpu_helpers import _dev, _Recorder  # noqa: E402
 
-DEV = 'cuda:0'
 F32 = np.float32
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # ------------------------------------------------------------------------------------------------ selection
@@ -254,17 +251,6 @@ def test_check_raises_on_nan_and_on_a_constant_volume():
     torch.cuda.synchronize()
 
 
-class _Recorder:
-    """Stands in for the library handle inside van_gan_amd.preprocess and notes which entries are called."""
-
-    def __init__(self, lib):
-        self._lib, self.names = lib, []
-
-    def __getattr__(self, name):
-        self.names.append(name)
-        return getattr(self._lib, name)
-
-
 def test_unchecked_call_makes_the_same_calls_whatever_the_data(monkeypatch):
     from van_gan_amd import preprocess
     a = _volume((37, 29, 23), 'uint8')
@@ -283,10 +269,7 @@ def test_unchecked_call_makes_the_same_calls_whatever_the_data(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ plumbing
-@functools.lru_cache(maxsize=None)
-def _engine():
-    from van_gan_amd import VanGan
-    return VanGan((32, 32, 32), batch_size=4, device=DEV, seed=5, precision='fp32')
+_engine = functools.lru_cache(maxsize=None)(gpu_helpers._engine)           # one engine per test module, as before
 
 
 def test_segment_volume_is_prepare_then_stitch(monkeypatch):

@@ -15,14 +15,11 @@ pytestmark = pytest.mark.gpu
 
 import lanczos_restate as R  # noqa: E402
 import preproc_restate as P  # noqa: E402
+import gpu_helpers  # noqa: E402
+from gpu_helpers import _dev, _raw, _Recorder as _NamesRecorder  # noqa: E402
 
-DEV = 'cuda:0'
 F32 = np.float32
 U9 = 9.0 * 2.0 ** -24
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -118,15 +115,15 @@ def test_vector_shape_from_a_misaligned_pointer():
 
 
 # ------------------------------------------------------------------------------------------------ whole volumes
-class _Recorder:
-    """Stands in for the library handle inside van_gan_amd.preprocess and notes the vg_resample_axis calls' (outer, L, inner, T)."""
+class _Recorder(_NamesRecorder):
+    """Also notes the vg_resample_axis calls' (outer, L, inner, T)."""
 
     def __init__(self, lib):
-        self._lib, self.calls, self.names = lib, [], []
+        super().__init__(lib)
+        self.calls = []
 
     def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        self.names.append(name)
+        fn = super().__getattr__(name)
         if name != 'vg_resample_axis':
             return fn
 
@@ -214,14 +211,6 @@ def test_integer_stacks_equal_their_float32_copy_bitwise(dtype):
 
 
 # ------------------------------------------------------------------------------------------------ prepare_imaging / segment_volume
-def _raw(dtype, shape=(24, 20, 35)):
-    rng = np.random.default_rng(len(dtype) + sum(shape))
-    top = 255 if dtype == 'uint8' else 65535
-    v = rng.gamma(2.0, 0.08, shape) * (1.0 + 0.3 * np.cos(np.arange(shape[2]) / 5.0))
-    v += (rng.random(shape) < 0.02) * rng.random(shape)
-    return np.clip(v * top, 0, top).astype(dtype)
-
-
 @pytest.mark.parametrize('dtype,pre', [('uint16', 'rsom'), ('uint8', None)])
 def test_prepare_imaging_with_a_target(dtype, pre, monkeypatch):
     from van_gan_amd.preprocess import prepare_imaging, preprocess_rsom_images, resize_volume
@@ -269,10 +258,7 @@ def test_check_keeps_its_messages_with_a_target():
     torch.cuda.synchronize()
 
 
-@functools.lru_cache(maxsize=None)
-def _engine():
-    from van_gan_amd import VanGan
-    return VanGan((32, 32, 32), batch_size=4, device=DEV, seed=5, precision='fp32')
+_engine = functools.lru_cache(maxsize=None)(gpu_helpers._engine)           # one engine per test module, as before
 
 
 def test_segment_volume_passes_the_target_through(monkeypatch):

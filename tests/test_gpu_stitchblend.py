@@ -13,12 +13,13 @@ pytestmark = pytest.mark.gpu
 import stitch_restate as R  # noqa: E402
 from oracle import stitch_oracle as S  # noqa: E402
 from oracle import vangan_oracle as O  # noqa: E402
+import gpu_helpers  # noqa: E402
+from gpu_helpers import DEV, _Recorder  # noqa: E402
 
 U = 2.0 ** -24
 K = (12, 10, 9)
 WINDOWS = [K, (8, 8, 16)]
 CROPS = [(1, 1, 0), (0, 0, 0)]
-DEV = 'cuda:0'
 
 
 def _rand(shape, seed):
@@ -155,10 +156,7 @@ def test_entry_checks_return_einval():
 
 
 # ------------------------------------------------------------------------------------------------ end to end
-@functools.lru_cache(maxsize=None)
-def _engine():
-    from van_gan_amd import VanGan
-    return VanGan((32, 32, 32), batch_size=4, device=DEV, seed=5, precision='fp32')
+_engine = functools.lru_cache(maxsize=None)(gpu_helpers._engine)           # one engine per test module, as before
 
 
 class Probe:
@@ -191,17 +189,6 @@ def _probe_vol():
 @functools.lru_cache(maxsize=None)
 def _probe_ref(blend, tta, process_img):
     return R.stitch(_probe_gen32, _probe_vol(), K, blend=blend, tta=tta, process_img=process_img, **PROBE_KW)
-
-
-class _Recorder:
-    """Stands in for the library handle inside van_gan_amd.inference and notes which entries the stitch calls."""
-
-    def __init__(self, lib):
-        self._lib, self.names = lib, []
-
-    def __getattr__(self, name):
-        self.names.append(name)
-        return getattr(self._lib, name)
 
 
 @pytest.mark.parametrize('process_img', [False, True])

@@ -26,6 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from tools.bench_preprocess import host_recipe, synth  # noqa: E402
+from tools.device_time import device_ms  # noqa: E402
 
 SIZES = [(256, 256, 128), (512, 512, 140)]
 DTYPES = ['uint8', 'uint16', 'float32']
@@ -60,24 +61,6 @@ def host_times(x32):
     return t, ref
 
 
-def device_ms(fn, iters, warmup, rounds):
-    import torch
-    out = None
-    for _ in range(warmup):
-        out = fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            out = fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1) / iters)
-    return float(np.median(times)), out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=50)
@@ -99,7 +82,7 @@ def main():
         n = int(np.prod(shape))
         src = torch.empty(n, device='cuda:0').normal_()
         dst = torch.empty_like(src)
-        copy_ms, _ = device_ms(lambda: dst.copy_(src), a.iters, a.warmup, a.rounds)
+        _, copy_ms, _ = device_ms(lambda: dst.copy_(src), a.iters, a.rounds, a.warmup)
         copy_rate = 8.0 * n / (copy_ms * 1e-3)
         del src, dst
         print('%s: fp32 copy %.4f ms, %.0f GB/s (read + written)' % (shape, copy_ms, copy_rate / 1e9), flush=True)
@@ -114,7 +97,7 @@ def main():
                     ('outliers', lambda: threshold_outliers(vol), False),
                     ('median_rsom', lambda: prepare_imaging(vol, preprocess=('median', 'rsom'), check=False), False))
             for name, fn, single_pass in runs:
-                ms, out = device_ms(fn, a.iters, a.warmup, a.rounds)
+                _, ms, out = device_ms(fn, a.iters, a.rounds, a.warmup)
                 case = dict(shape=list(shape), dtype=dtype, op=name, voxels=n, device_ms=round(ms, 4), copy_gbytes_per_s=round(copy_rate / 1e9, 1))
                 line = '%s %-7s %-11s device %.4f ms' % (shape, dtype, name, ms)
                 if single_pass:

@@ -17,6 +17,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from tools.device_time import device_ms  # noqa: E402
+
 SIZES = [(256, 256, 128), (512, 512, 140)]
 COPY_RATE = 6.3e12           # bytes / s: what a float4 copy measures on the MI355X (the HBM3E specification is 8.0e12)
 RESIZE = 1.3                 # case (b): every axis grows by this factor (rounded)
@@ -109,16 +111,7 @@ def main():
                 stack = raw if tgt is None else np.clip(resize_volume(vol, tgt).cpu().numpy(), 0, 255)      # the host is timed on the device's resize
                 host_s, ref = host_recipe(stack)
                 same = bool(np.array_equal(out.cpu().numpy()[..., 0], ref))
-            rounds = []
-            for _ in range(a.rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(a.iters):
-                    out = prepare_segmentation(vol, check=False, target_size=tgt)
-                e1.record()
-                e1.synchronize()
-                rounds.append(e0.elapsed_time(e1) / a.iters)
-            med = float(np.median(rounds))
+            rounds, med, out = device_ms(lambda: prepare_segmentation(vol, check=False, target_size=tgt), a.iters, a.rounds)
             nbytes = pass_bytes(n_in, esz, n, passes)
             floor_ms = nbytes / COPY_RATE * 1e3
             case = dict(case=name, shape=list(shape), out_shape=list(out_shape), voxels=n, device_ms_rounds=[round(r, 4) for r in rounds],
@@ -137,15 +130,7 @@ def main():
     from van_gan_amd.preprocess import value_mode
     for shape in shapes:
         x = torch.from_numpy(synth_distinct(shape)).to('cuda:0')
-        for _ in range(a.warmup):
-            value_mode(x)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            value_mode(x)
-        e1.record()
-        e1.synchronize()
-        ms = e0.elapsed_time(e1) / a.iters
+        ms = device_ms(lambda: value_mode(x), a.iters, 1, a.warmup)[1]
         print('%s value_mode, all distinct: %.3f ms, %.3g inserts / s' % (shape, ms, x.numel() / (ms * 1e-3)), flush=True)
         res['cases'].append(dict(case='value_mode-distinct-fp32', shape=list(shape), device_ms=round(ms, 4), inserts_per_s=round(x.numel() / (ms * 1e-3), 0)))
         del x

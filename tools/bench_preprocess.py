@@ -18,6 +18,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from tools.device_time import device_ms  # noqa: E402
+
 SIZES = [(256, 256, 128), (512, 512, 140)]
 DTYPES = ['uint8', 'uint16']
 HBM_PEAK = 8.0e12            # bytes / s, the MI355X's HBM3E specification; a float4 copy measures 6.3e12
@@ -89,20 +91,11 @@ def main():
                 out = prepare_imaging(vol, check=False)
             torch.cuda.synchronize()
             err = float(np.abs(out.cpu().numpy()[..., 0].astype(np.float64) - ref).max())      # the host recipe is fp32: agreement, not parity
-            rounds = []
-            for _ in range(a.rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(a.iters):
-                    out = prepare_imaging(vol, check=False)
-                e1.record()
-                e1.synchronize()
-                rounds.append(e0.elapsed_time(e1) / a.iters)
+            rounds, med, out = device_ms(lambda: prepare_imaging(vol, check=False), a.iters, a.rounds)
             t0 = time.perf_counter()
             for _ in range(a.iters):
                 prepare_imaging(vol, check=True)
             checked_ms = (time.perf_counter() - t0) * 1e3 / a.iters
-            med = float(np.median(rounds))
             case = dict(shape=list(shape), dtype=dtype, voxels=n, device_ms_rounds=[round(r, 4) for r in rounds], device_ms=round(med, 4),
                         checked_wall_ms=round(checked_ms, 4), upload_ms=round(upload_ms, 3), pass_bytes=pass_bytes(n, esz),
                         gbytes_per_s=round(pass_bytes(n, esz) / (med * 1e-3) / 1e9, 1),

@@ -19,6 +19,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from tools.device_time import device_ms  # noqa: E402
+
 CASES = '512x512x140:512x512x128,512x512x140:256x256x128'
 COPY_RATE = 6.3e12           # bytes / s: what a float4 copy measures on an MI355X (the HBM3E specification is 8.0e12)
 
@@ -43,20 +45,8 @@ def passes(shape, target):
 
 
 def timed(fn, warmup, iters, rounds):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1) / iters)
-    return [round(m, 4) for m in ms], float(np.median(ms))
+    ms, med, _ = device_ms(fn, iters, rounds, warmup)
+    return [round(m, 4) for m in ms], med
 
 
 def rate(nbytes, ms):

@@ -1,17 +1,10 @@
 // vg_filters.hip -- imaging filters (van_gan_amd/preprocess.py; include/vangan_hip.h "Imaging filters"): the 3-D / slice-wise
-// median of a uint8 / uint16 / float32 volume [X][Y][Z] (Z innermost) with scipy's 'reflect' boundary, the moments of a whole volume, and
-// the selection half of threshold_outliers (utils.py:108-133): the extreme values within `threshold` standard deviations of the mean.
+// median of a uint8 / uint16 / float32 volume [X][Y][Z] (Z innermost) with scipy's 'reflect' boundary, and the selection half of
+// threshold_outliers (utils.py:108-133): the extreme values within `threshold` standard deviations of the mean (the moments of the whole
+// volume, vg_volume_moments, are in vg_preproc.hip beside the slice moments).  What is shared with the other preprocessing files: vg_volume.h.
 // Nothing here depends on the 16-bit storage format of the build.  256-thread workgroups (4 wave64); only integer atomics are used, so
 // every result is bitwise reproducible.
-#include "vg_common.h"
-
-static inline bool mf_dtype_ok(int dtype) { return dtype == VG_PP_U8 || dtype == VG_PP_U16 || dtype == VG_PP_F32; }
-static inline int mf_esz(int dtype) { return dtype == VG_PP_U8 ? 1 : dtype == VG_PP_U16 ? 2 : 4; }
-static inline int mf_blocks(int64_t threads) { int64_t b = (threads + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
-
-template <typename T, int V> struct alignas(sizeof(T) * V) mf_pack { T v[V]; };     // one load of V elements
-
-__device__ __forceinline__ unsigned mf_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+#include "vg_volume.h"
 
 // ------------------------------------------------------------------------------------------------ median
 // A workgroup owns a tile of MF_TY x MF_TZ outputs in (y, z) -- thread t is (y, z) = (t / MF_TZ, t % MF_TZ), so a wave covers two rows of 32
@@ -189,7 +182,7 @@ __global__ __launch_bounds__(256) void median3_kernel(const T* __restrict__ vol,
 #pragma unroll
                 for (int dz = 0; dz < SZ; ++dz) nw[dy * SZ + dz] = buf[(ty + dy) * PW + tz + dz];
             if constexpr (sizeof(T) == 4)                           // the voxel itself, counted once: in the planes this tile writes
-                if (active && s >= HX && s < np - HX) bad += mf_nonfinite(nw[HY * SZ + HZ]);
+                if (active && s >= HX && s < np - HX) bad += vol_nonfinite(nw[HY * SZ + HZ]);
             mf_prep<SX, P>(nw);
 #pragma unroll
             for (int i = 0; i < M - P; ++i) w[i] = w[i + P];
@@ -226,7 +219,7 @@ static void median3_launch(const void* vol, int X, int Y, int Z, float* out, uin
 }
 
 template <typename T>
-static void median3_dispatch(const void* vol, int X, int Y, int Z, int sx, int sy, int sz, float* out, uint32_t* nonfinite, hipStream_t s) {
+static void median3_dispatch(const T* vol, int X, int Y, int Z, int sx, int sy, int sz, float* out, uint32_t* nonfinite, hipStream_t s) {
     switch ((sx == 3 ? 4 : 0) | (sy == 3 ? 2 : 0) | (sz == 3 ? 1 : 0)) {
     case 0: median3_launch<T, 1, 1, 1>(vol, X, Y, Z, out, nonfinite, s); break;
     case 1: median3_launch<T, 1, 1, 3>(vol, X, Y, Z, out, nonfinite, s); break;
@@ -242,104 +235,21 @@ static void median3_dispatch(const void* vol, int X, int Y, int Z, int sx, int s
 extern "C" int vg_median3(const void* vol, int dtype, int X, int Y, int Z, int sx, int sy, int sz, float* out, uint32_t* nonfinite,
                           vg_stream_t stream) {
     vg_begin();
-    if (!vol || !out || !nonfinite || !mf_dtype_ok(dtype) || X < 1 || Y < 1 || Z < 1 || Z > (1 << 20)) return VG_EINVAL;
+    if (!vol || !out || !nonfinite || !vol_dtype_ok(dtype) || X < 1 || Y < 1 || Z < 1 || Z > (1 << 20)) return VG_EINVAL;
     if ((int64_t)X * Y >= ((int64_t)1 << 40)) return VG_EINVAL;
     if ((sx != 1 && sx != 3) || (sy != 1 && sy != 3) || (sz != 1 && sz != 3)) return VG_EINVAL;
     const int64_t n = (int64_t)X * Y * Z;
     const uintptr_t v0 = (uintptr_t)vol, o0 = (uintptr_t)out;
-    if (v0 % mf_esz(dtype) != 0 || o0 % 4 != 0 || (uintptr_t)nonfinite % 4 != 0) return VG_EINVAL;
-    if (v0 < o0 + (uintptr_t)n * 4 && o0 < v0 + (uintptr_t)n * mf_esz(dtype)) return VG_EINVAL;        // out overlaps vol
+    if (v0 % vol_esz(dtype) != 0 || o0 % 4 != 0 || (uintptr_t)nonfinite % 4 != 0) return VG_EINVAL;
+    if (v0 < o0 + (uintptr_t)n * 4 && o0 < v0 + (uintptr_t)n * vol_esz(dtype)) return VG_EINVAL;        // out overlaps vol
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == VG_PP_U8) median3_dispatch<uint8_t>(vol, X, Y, Z, sx, sy, sz, out, nonfinite, s);
-    else if (dtype == VG_PP_U16) median3_dispatch<uint16_t>(vol, X, Y, Z, sx, sy, sz, out, nonfinite, s);
-    else median3_dispatch<float>(vol, X, Y, Z, sx, sy, sz, out, nonfinite, s);
-    return vg_check_launch();
-}
-
-// ------------------------------------------------------------------------------------------------ moments of the whole volume
-// vg_slice_moments' accumulation on one flat array: fp64 sums of d = x - vol[0] and of d * d per thread (grid-strided, four elements per
-// load where the pointer allows), added through LDS in a fixed tree; the workgroup's pair goes to part[blockIdx.x].
-#define MF_MOMENT_BLOCKS 2048
-
-template <typename T>
-__global__ __launch_bounds__(256) void volume_moments_kernel(const T* __restrict__ vol, int64_t n, int vec, double* __restrict__ part) {
-    __shared__ double red[2][256];
-    const int t = threadIdx.x;
-    const int64_t tid = (int64_t)blockIdx.x * 256 + t, nthr = (int64_t)gridDim.x * 256;
-    const double piv = (double)vol[0];
-    const int64_t nv = vec ? n / 4 : 0;
-    double s = 0.0, q = 0.0;
-    for (int64_t i = tid; i < nv; i += nthr) {
-        const mf_pack<T, 4> p = *(const mf_pack<T, 4>*)(vol + i * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const double d = (double)p.v[j] - piv; s += d; q += d * d; }
-    }
-    for (int64_t e = nv * 4 + tid; e < n; e += nthr) { const double d = (double)vol[e] - piv; s += d; q += d * d; }
-    red[0][t] = s; red[1][t] = q;
-    __syncthreads();
-#pragma unroll
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; }
-        __syncthreads();
-    }
-    if (t == 0) { part[2 * blockIdx.x] = red[0][0]; part[2 * blockIdx.x + 1] = red[1][0]; }
-}
-
-__device__ __forceinline__ double mf_load1(const void* vol, int dtype) {
-    if (dtype == VG_PP_U8) return (double)*(const uint8_t*)vol;
-    if (dtype == VG_PP_U16) return (double)*(const uint16_t*)vol;
-    return (double)*(const float*)vol;
-}
-
-// One wave: lane l adds the partials of workgroups l, l + 64, ... in ascending order, then a butterfly (both partners form the same sum) --
-// a fixed association.  mean = pivot + S / n, var = Q / n - (S / n)^2, each rounded once to fp32.
-__global__ __launch_bounds__(64) void volume_moments_final_kernel(const double* __restrict__ part, int nb, int64_t n, const void* __restrict__ vol,
-                                                                  int dtype, float* __restrict__ mean_std) {
-    const int lane = threadIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int b = lane; b < nb; b += 64) { s += part[2 * b]; q += part[2 * b + 1]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
-    if (lane == 0) {
-        const double nn = (double)n, ms = s / nn;
-        double var = q / nn - ms * ms;
-        if (var < 0.0) var = 0.0;                                   // a NaN stays a NaN
-        mean_std[0] = (float)(mf_load1(vol, dtype) + ms);
-        mean_std[1] = (float)sqrt(var);
-    }
-}
-
-static inline bool mf_n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 60); }
-
-extern "C" int64_t vg_volume_moments_scratch_bytes(int64_t n) {
-    if (!mf_n_ok(n)) return VG_EINVAL;
-    return (int64_t)MF_MOMENT_BLOCKS * 2 * (int64_t)sizeof(double);
-}
-
-extern "C" int vg_volume_moments(const void* vol, int dtype, int64_t n, float* mean_std, void* scratch, int64_t scratch_bytes,
-                                 vg_stream_t stream) {
-    vg_begin();
-    if (!vol || !mean_std || !scratch || !mf_n_ok(n) || !mf_dtype_ok(dtype)) return VG_EINVAL;
-    if (scratch_bytes < vg_volume_moments_scratch_bytes(n) || (uintptr_t)scratch % 16 != 0 || (uintptr_t)mean_std % 4 != 0) return VG_EINVAL;
-    const int esz = mf_esz(dtype);
-    if ((uintptr_t)vol % esz != 0) return VG_EINVAL;
-    const int vec = (uintptr_t)vol % (4 * esz) == 0;
-    const int nb = mf_blocks(vec ? (n + 3) / 4 : n);
-    hipStream_t s = (hipStream_t)stream;
-    double* part = (double*)scratch;
-    if (dtype == VG_PP_U8) hipLaunchKernelGGL(volume_moments_kernel<uint8_t>, dim3(nb), dim3(256), 0, s, (const uint8_t*)vol, n, vec, part);
-    else if (dtype == VG_PP_U16) hipLaunchKernelGGL(volume_moments_kernel<uint16_t>, dim3(nb), dim3(256), 0, s, (const uint16_t*)vol, n, vec, part);
-    else hipLaunchKernelGGL(volume_moments_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)vol, n, vec, part);
-    hipLaunchKernelGGL(volume_moments_final_kernel, dim3(1), dim3(64), 0, s, part, nb, n, vol, dtype, mean_std);
+    vol_dispatch(vol, dtype, [&](auto* v) { median3_dispatch(v, X, Y, Z, sx, sy, sz, out, nonfinite, s); });
     return vg_check_launch();
 }
 
 // ------------------------------------------------------------------------------------------------ outlier limits
-// The order-preserving key of vg_order_stats (vg_preproc.hip): unsigned order == float order, -0.0 directly below +0.0.
-__device__ __forceinline__ unsigned mf_key(float f) { const unsigned b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ float mf_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-// While the scan runs, stats4[0] and stats4[2] hold the smallest and the largest key met, as integers; the last kernel turns them into values.
+// While the scan runs, stats4[0] and stats4[2] hold the smallest and the largest key met (vol_key: unsigned order == float order), as
+// integers; the last kernel turns them into values.
 __global__ void outlier_init_kernel(unsigned* __restrict__ keys, unsigned* __restrict__ kn2) {
     keys[0] = 0xffffffffu; keys[1] = 0xffffffffu; keys[2] = 0u; keys[3] = 0u;
     kn2[0] = 0u;
@@ -352,12 +262,12 @@ struct mf_keep { unsigned kmin, kmax, bad; unsigned long long kept; };
 __device__ __forceinline__ void mf_keep1(float x, float m, float s, float thr, mf_keep& k) {
     const float z = __builtin_fabsf((x - m) / s);
     if (z <= thr) {
-        const unsigned key = mf_key(x);
+        const unsigned key = vol_key(x);
         k.kmin = key < k.kmin ? key : k.kmin;
         k.kmax = key > k.kmax ? key : k.kmax;
         ++k.kept;
     }
-    k.bad += mf_nonfinite(x);
+    k.bad += vol_nonfinite(x);
 }
 
 template <typename T>
@@ -371,7 +281,7 @@ __global__ __launch_bounds__(256) void outlier_scan_kernel(const T* __restrict__
     const int64_t nv = vec ? n / 4 : 0;
     mf_keep k = {0xffffffffu, 0u, 0u, 0ull};
     for (int64_t i = tid; i < nv; i += nthr) {
-        const mf_pack<T, 4> p = *(const mf_pack<T, 4>*)(vol + i * 4);
+        const vol_pack<T, 4> p = *(const vol_pack<T, 4>*)(vol + i * 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) mf_keep1((float)p.v[j], m, s, thr, k);
     }
@@ -412,25 +322,25 @@ __global__ void outlier_finish_kernel(float* __restrict__ stats4, const unsigned
     const unsigned* keys = (const unsigned*)stats4;
     const unsigned k0 = keys[0], k2 = keys[2];
     const bool any = kn2[0] != 0u;
-    const float lo = any ? mf_unkey(k0) : __builtin_inff(), hi = any ? mf_unkey(k2) : -__builtin_inff();
+    const float lo = any ? vol_unkey(k0) : __builtin_inff(), hi = any ? vol_unkey(k2) : -__builtin_inff();
     stats4[0] = lo; stats4[1] = lo; stats4[2] = hi; stats4[3] = hi;
 }
 
 extern "C" int vg_outlier_limits(const void* vol, int dtype, int64_t n, const float* mean_std, float threshold, float* stats4,
                                  uint32_t* kept_nonfinite2, vg_stream_t stream) {
     vg_begin();
-    if (!vol || !mean_std || !stats4 || !kept_nonfinite2 || !mf_n_ok(n) || !mf_dtype_ok(dtype)) return VG_EINVAL;
+    if (!vol || !mean_std || !stats4 || !kept_nonfinite2 || !vol_n_ok(n) || !vol_dtype_ok(dtype)) return VG_EINVAL;
     if (!(threshold > 0.f) || !(threshold < __builtin_inff())) return VG_EINVAL;
-    const int esz = mf_esz(dtype);
+    const int esz = vol_esz(dtype);
     if ((uintptr_t)vol % esz != 0 || (uintptr_t)mean_std % 4 != 0 || (uintptr_t)stats4 % 4 != 0 || (uintptr_t)kept_nonfinite2 % 4 != 0) return VG_EINVAL;
     const int vec = (uintptr_t)vol % (4 * esz) == 0;
-    const dim3 grid(mf_blocks(vec ? (n + 3) / 4 : n)), block(256);
     hipStream_t s = (hipStream_t)stream;
     unsigned* keys = (unsigned*)stats4;
     hipLaunchKernelGGL(outlier_init_kernel, dim3(1), dim3(1), 0, s, keys, kept_nonfinite2);
-    if (dtype == VG_PP_U8) hipLaunchKernelGGL(outlier_scan_kernel<uint8_t>, grid, block, 0, s, (const uint8_t*)vol, n, vec, mean_std, threshold, keys, kept_nonfinite2);
-    else if (dtype == VG_PP_U16) hipLaunchKernelGGL(outlier_scan_kernel<uint16_t>, grid, block, 0, s, (const uint16_t*)vol, n, vec, mean_std, threshold, keys, kept_nonfinite2);
-    else hipLaunchKernelGGL(outlier_scan_kernel<float>, grid, block, 0, s, (const float*)vol, n, vec, mean_std, threshold, keys, kept_nonfinite2);
+    vol_dispatch(vol, dtype, [&](auto* v) {
+        hipLaunchKernelGGL(outlier_scan_kernel<vol_elem_t<decltype(v)>>, vol_grid(n, vec), dim3(256), 0, s, v, n, vec, mean_std, threshold, keys,
+                           kept_nonfinite2);
+    });
     hipLaunchKernelGGL(outlier_finish_kernel, dim3(1), dim3(1), 0, s, stats4, kept_nonfinite2);
     return vg_check_launch();
 }

@@ -5,7 +5,7 @@
 // 256-thread workgroups (4 wave64), grid-strided.  Only integer atomics, and every reduction is a sum or a maximum of integers: the result
 // words are bitwise reproducible whatever slot a key lands in.  Every probe loop is bounded by the slot count of its table; no workgroup
 // waits on another.
-#include "vg_common.h"
+#include "vg_volume.h"
 
 #pragma clang fp contract(off)             // the whole file: every fp32 operation below is rounded on its own, as numpy rounds it
 
@@ -20,10 +20,6 @@
 #define LP_BLOCK_ELEMS 8192                 // a workgroup is given at least this many elements (one combiner flush per workgroup)
 #define LP_ONE 0x3f800000u
 
-static inline int lp_blocks(int64_t items, int64_t per_block) {
-    const int64_t b = (items + per_block - 1) / per_block;
-    return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
 static inline bool lp_n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 31); }
 static inline int64_t lp_slots(int64_t n) { int64_t s = 2; while (s < 2 * n) s <<= 1; return s; }      // a power of two >= 2 n: load <= 0.5
 
@@ -32,11 +28,9 @@ __device__ __forceinline__ unsigned lp_hash(unsigned k) {
     k ^= k >> 16; k *= 0x85ebca6bu; k ^= k >> 13; k *= 0xc2b2ae35u; k ^= k >> 16;
     return k;
 }
-// unsigned order == float order (vg_preproc.hip's pp_key); inverted below so that the larger packed word is the SMALLER value
-__device__ __forceinline__ unsigned lp_okey(unsigned b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ unsigned lp_unkey(unsigned k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
+// the order key (vol_key_bits) inverted, so that the larger packed word is the SMALLER value
 __device__ __forceinline__ unsigned long long lp_pack(unsigned bits, unsigned count) {
-    return ((unsigned long long)count << 32) | (unsigned)~lp_okey(bits);
+    return ((unsigned long long)count << 32) | (unsigned)~vol_key_bits(bits);
 }
 
 // count[key] += c in the global table: linear probing from the key's hash, at most one probe per slot.  A slot's key never changes once
@@ -66,7 +60,7 @@ __device__ __forceinline__ void lp_count1(float v, bool norm, float mn, float rn
                                           unsigned mask, unsigned* hdr, lp_acc& a) {
     const float y = norm ? (v - mn) / rng : v;                      // numpy's (x - min) / (max - min): three roundings, no reciprocal
     unsigned b = __float_as_uint(y);
-    if ((b & 0x7f800000u) == 0x7f800000u) { ++a.bad; return; }
+    if (vol_nonfinite_bits(b)) { ++a.bad; return; }
     if ((b << 1) == 0u) { ++a.c0; return; }                         // -0.0 and +0.0 are one value
     if (b == LP_ONE) { ++a.c1; return; }
     unsigned s = lp_hash(b) & (VG_MODE_LDS_SLOTS - 1);
@@ -153,7 +147,7 @@ __global__ void lp_final_kernel(const unsigned* __restrict__ hdr, unsigned* __re
     if (hdr[LP_C0]) { const unsigned long long c = lp_pack(0u, hdr[LP_C0]); m = c > m ? c : m; }
     if (hdr[LP_C1]) { const unsigned long long c = lp_pack(LP_ONE, hdr[LP_C1]); m = c > m ? c : m; }
     const unsigned count = (unsigned)(m >> 32);
-    result4[0] = count ? lp_unkey(~(unsigned)m) : 0x7fc00000u;      // no finite value at all: count 0 and a NaN
+    result4[0] = count ? __float_as_uint(vol_unkey(~(unsigned)m)) : 0x7fc00000u;      // no finite value at all: count 0 and a NaN
     result4[1] = count;
     result4[2] = hdr[LP_STATUS];
     result4[3] = hdr[LP_BAD];
@@ -175,9 +169,9 @@ extern "C" int vg_value_mode(const float* x, int64_t n, const float* mm4_or_null
     unsigned* tab = hdr + LP_HDR_WORDS;
     const int64_t slots = lp_slots(n), npairs = slots / 2;
     const unsigned mask = (unsigned)(slots - 1);
-    const dim3 block(256), sweep(lp_blocks(npairs, 256 * 8));
+    const dim3 block(256), sweep(vol_blocks(npairs, 256 * 8));
     hipLaunchKernelGGL(lp_init_kernel, sweep, block, 0, s, hdr, npairs);
-    const dim3 grid(lp_blocks(n, LP_BLOCK_ELEMS));
+    const dim3 grid(vol_blocks(n, LP_BLOCK_ELEMS));
     if ((uintptr_t)x % 16 == 0) hipLaunchKernelGGL(lp_count_kernel<4>, grid, block, 0, s, x, n, mm4_or_null, hdr, tab, mask);
     else hipLaunchKernelGGL(lp_count_kernel<1>, grid, block, 0, s, x, n, mm4_or_null, hdr, tab, mask);
     hipLaunchKernelGGL(lp_reduce_kernel, sweep, block, 0, s, hdr, npairs, (unsigned long long*)(hdr + LP_BEST));
@@ -222,7 +216,6 @@ extern "C" int vg_label_finish(const float* x, int64_t n, const float* mm4, cons
     if ((uintptr_t)x % 4 != 0 || (uintptr_t)mm4 % 4 != 0 || (uintptr_t)result4 % 4 != 0 || (uintptr_t)out % 4 != 0 || (uintptr_t)state % 4 != 0)
         return VG_EINVAL;
     const int vec = (uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0;
-    hipLaunchKernelGGL(lp_finish_kernel, dim3(lp_blocks(vec ? (n + 3) / 4 : n, 256)), dim3(256), 0, (hipStream_t)stream, x, n, mm4, result4, out,
-                       state, vec);
+    hipLaunchKernelGGL(lp_finish_kernel, vol_grid(n, vec), dim3(256), 0, (hipStream_t)stream, x, n, mm4, result4, out, state, vec);
     return vg_check_launch();
 }

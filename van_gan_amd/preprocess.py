@@ -47,10 +47,12 @@ class RawVolume:
         return self.nxy * self.shape[2]
 
 
+def _drop_channel(sizes: tuple) -> tuple:                      # [a, b, c, 1] -> [a, b, c]: the trailing 1 of a volume's shape is tolerated
+    return sizes[:3] if len(sizes) == 4 and sizes[3] == 1 else sizes
+
+
 def _shape3(shape) -> Tuple[int, int, int]:
-    shape = tuple(int(s) for s in shape)
-    if len(shape) == 4 and shape[3] == 1:
-        shape = shape[:3]
+    shape = _drop_channel(tuple(int(s) for s in shape))
     if len(shape) != 3:
         raise ValueError('a volume is [X,Y,Z] or [X,Y,Z,1], got shape %s' % (shape,))
     if min(shape) < 1:
@@ -98,12 +100,17 @@ def as_raw_volume(raw, device=None) -> RawVolume:
     return RawVolume(t.to(_resolve_device(device, given)), code, shape)
 
 
+def _scratch(query: str, *args, dev) -> Tuple[torch.Tensor, int]:
+    """(buffer, bytes): the scratch an entry point needs for these sizes, as its query `query` (vg_..._scratch_bytes) tells; allocated as
+    that many bytes (torch aligns every allocation to 512 bytes, the entries ask for 16)."""
+    nbytes = int(getattr(lib, query)(*args))
+    _check(nbytes, query)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
 def _moments_into(v: RawVolume, ms: torch.Tensor) -> None:
-    X, Y, Z = v.shape
-    nbytes = int(lib.vg_slice_moments_scratch_bytes(v.nxy, Z))
-    _check(nbytes, 'vg_slice_moments_scratch_bytes')
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=v.buf.device)
-    _check(lib.vg_slice_moments(_p(v.buf), v.code, v.nxy, Z, _p(ms), _p(scratch), nbytes, stream()), 'vg_slice_moments')
+    scratch, nbytes = _scratch('vg_slice_moments_scratch_bytes', v.nxy, v.shape[2], dev=v.buf.device)
+    _check(lib.vg_slice_moments(_p(v.buf), v.code, v.nxy, v.shape[2], _p(ms), _p(scratch), nbytes, stream()), 'vg_slice_moments')
 
 
 def _zscore_into(v: RawVolume, ms: torch.Tensor, out: torch.Tensor, counter_ptr: int) -> None:
@@ -141,9 +148,7 @@ def _dev_f32(x, what='x') -> torch.Tensor:
 
 def _order_stats_into(x: torch.Tensor, ranks: Sequence[int], out_ptr: int) -> None:
     n, R = x.numel(), len(ranks)
-    nbytes = int(lib.vg_order_stats_scratch_bytes(n, R))
-    _check(nbytes, 'vg_order_stats_scratch_bytes')
-    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
+    scratch, nbytes = _scratch('vg_order_stats_scratch_bytes', n, R, dev=x.device)
     rk = (C.c_int64 * R)(*ranks)
     _check(lib.vg_order_stats(_p(x), n, rk, R, out_ptr, _p(scratch), nbytes, stream()), 'vg_order_stats')
 
@@ -206,10 +211,35 @@ def _clip_into(z: torch.Tensor, lower_thresh: float, upper_thresh: float, rescal
     _check(lib.vg_clip_rescale(_p(z), n, _p(stats), lo[2], hi[2], 1 if rescale else 0, limits_ptr, _p(out), stream()), 'vg_clip_rescale')
 
 
+# The words of a status block (_state_block).  Words 4 and 5 mean one thing in prepare_imaging's block and another in prepare_segmentation's.
+W_NONFINITE, W_INVERTED, W_LO, W_HI = 0, 1, 2, 3     # the non-finite counter, the inversion flag of a label volume, the fp32 limits (lp, up)
+W_KEPT, W_KEPT_NONFINITE = 4, 5                     # imaging: the kept and the non-finite count of the 'outliers' stage
+W_MODE, W_MODE_COUNT, W_MODE_STATUS = 4, 5, 6       # labels: the mode's value (fp32 bits), its count, vg_value_mode's status
+
+
 def _state_block(dev, words: int = 4) -> torch.Tensor:
-    """32-bit words read back in one copy: [0] the non-finite counter, [2], [3] the fp32 limits (lp, up); with words=8 also [4], [5] the
-    kept and the non-finite count of an 'outliers' stage."""
+    """32-bit words on the device that the kernels fill and one copy reads back, zeroed: prepare_imaging uses 4, and 8 with an 'outliers'
+    stage (vg_outlier_limits writes two); prepare_segmentation's words 1 to 7 are written by vg_label_finish."""
     return torch.zeros(words, dtype=torch.int32, device=dev)
+
+
+def _word(state: torch.Tensor, w: int) -> int:                # the device address of word w
+    return _p(state) + 4 * w
+
+
+def _read_state(state: torch.Tensor, check: bool = True, outliers: bool = False):
+    """(words, lp, up): the status block on the host (a synchronising copy) and its two limits; check: raises what both recipes raise.
+    outliers: prepare_imaging's block with an 'outliers' stage, whose words 4 and 5 are checked too (never a label block)."""
+    host = state.cpu()
+    lo, hi = (float(x) for x in host[W_LO:W_HI + 1].view(torch.float32))
+    if check:
+        if int(host[W_NONFINITE]) != 0 or (outliers and int(host[W_KEPT_NONFINITE]) != 0):
+            raise ValueError('NaN detected')
+        if outliers and int(host[W_KEPT]) == 0:
+            raise ValueError(OUTLIERS_ERROR)
+        if lo == hi:
+            raise ValueError(MINMAX_ERROR)
+    return host, lo, hi
 
 
 def preprocess_rsom_images(vol, lower_thresh: float = 0.05, upper_thresh: float = 99.95, device=None) -> torch.Tensor:
@@ -223,8 +253,8 @@ def preprocess_rsom_images(vol, lower_thresh: float = 0.05, upper_thresh: float 
         ms = torch.empty(v.shape[2], 2, device=dev)
         z = torch.empty(v.shape, device=dev)
         _moments_into(v, ms)
-        _zscore_into(v, ms, z, _p(state))
-        _clip_into(z, lower_thresh, upper_thresh, False, _p(state) + 8, z)
+        _zscore_into(v, ms, z, _word(state, W_NONFINITE))
+        _clip_into(z, lower_thresh, upper_thresh, False, _word(state, W_LO), z)
     return z
 
 
@@ -291,11 +321,9 @@ def lanczos4_table(L: int, T: int) -> Tuple[np.ndarray, np.ndarray]:
 def _target3(target_size) -> Tuple[int, int, int]:
     """Three integers >= 1 (a trailing 1 is tolerated, as in a volume's shape)."""
     try:
-        tgt = tuple(operator.index(s) for s in target_size)
+        tgt = _drop_channel(tuple(operator.index(s) for s in target_size))
     except TypeError:
         raise ValueError('target_size is three integers, got %r' % (target_size,)) from None
-    if len(tgt) == 4 and tgt[3] == 1:
-        tgt = tgt[:3]
     if len(tgt) != 3 or min(tgt) < 1 or max(tgt) > MAX_AXIS:
         raise ValueError('target_size is three integers in [1, 2^20], got %r' % (target_size,))
     return tgt
@@ -362,7 +390,7 @@ def resize_volume(vol, target_size, device=None) -> torch.Tensor:
     v = as_raw_volume(vol, device)
     dev = v.buf.device
     with torch.cuda.device(dev):
-        x = v.buf.view(v.shape) if v.code == PP_F32 else _to_f32(v, _p(_state_block(dev)))
+        x = v.buf.view(v.shape) if v.code == PP_F32 else _to_f32(v, _word(_state_block(dev), W_NONFINITE))
         return _resize_f32(x, tgt)
 
 
@@ -415,9 +443,7 @@ def _median_into(v: RawVolume, size3: Tuple[int, int, int], counter_ptr: int) ->
 
 
 def _volume_moments_into(v: RawVolume, ms: torch.Tensor) -> None:
-    nbytes = int(lib.vg_volume_moments_scratch_bytes(v.numel))
-    _check(nbytes, 'vg_volume_moments_scratch_bytes')
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=v.buf.device)
+    scratch, nbytes = _scratch('vg_volume_moments_scratch_bytes', v.numel, dev=v.buf.device)
     _check(lib.vg_volume_moments(_p(v.buf), v.code, v.numel, _p(ms), _p(scratch), nbytes, stream()), 'vg_volume_moments')
 
 
@@ -431,12 +457,12 @@ def _outlier_limits_into(v: RawVolume, threshold: float, stats: torch.Tensor, co
 def _outliers_into(v: RawVolume, threshold: float, rescale: bool, state: torch.Tensor) -> torch.Tensor:
     """threshold_outliers of v as a new fp32 tensor (optionally with the rescale to [-1, 1]); state: the 8-word block of prepare_imaging."""
     stats = torch.empty(4, device=v.buf.device)
-    _outlier_limits_into(v, threshold, stats, _p(state) + 16)
+    _outlier_limits_into(v, threshold, stats, _word(state, W_KEPT))
     if v.code == PP_F32:
         x, out = v.buf.view(v.shape), torch.empty(v.shape, device=v.buf.device)
     else:
-        x = out = _to_f32(v, _p(state))
-    _check(lib.vg_clip_rescale(_p(x), v.numel, _p(stats), 0.0, 0.0, 1 if rescale else 0, _p(state) + 8, _p(out), stream()), 'vg_clip_rescale')
+        x = out = _to_f32(v, _word(state, W_NONFINITE))
+    _check(lib.vg_clip_rescale(_p(x), v.numel, _p(stats), 0.0, 0.0, 1 if rescale else 0, _word(state, W_LO), _p(out), stream()), 'vg_clip_rescale')
     return out
 
 
@@ -534,31 +560,24 @@ def prepare_imaging(raw, preprocess='rsom', lower_thresh: float = 0.05, upper_th
         for i, stage in enumerate(stages):
             rescale = fused and i == len(stages) - 1
             if stage == 'median':
-                out = _median_into(v, size3, _p(state))
+                out = _median_into(v, size3, _word(state, W_NONFINITE))
             elif stage == 'outliers':
                 out = _outliers_into(v, thr, rescale, state)
             else:
                 ms = torch.empty(v.shape[2], 2, device=dev)
                 out = torch.empty(v.shape, device=dev)
                 _moments_into(v, ms)
-                _zscore_into(v, ms, out, _p(state))
-                _clip_into(out, lower_thresh, upper_thresh, rescale, _p(state) + 8, out)
+                _zscore_into(v, ms, out, _word(state, W_NONFINITE))
+                _clip_into(out, lower_thresh, upper_thresh, rescale, _word(state, W_LO), out)
             v = RawVolume(out, PP_F32, v.shape)
         if not stages:
-            out = _to_f32(v, _p(state))
+            out = _to_f32(v, _word(state, W_NONFINITE))
         if tgt is not None:
             out = _resize_f32(out, tgt)                 # `out` itself when no axis changes: ours, so the rescale below may run in place
         if not fused:
-            _minmax_rescale(out, _p(state) + 8)
+            _minmax_rescale(out, _word(state, W_LO))
         if check:
-            host = state.cpu()
-            if int(host[0]) != 0 or (outliers and int(host[5]) != 0):
-                raise ValueError('NaN detected')
-            if outliers and int(host[4]) == 0:
-                raise ValueError(OUTLIERS_ERROR)
-            lims = host[2:4].view(torch.float32)
-            if float(lims[0]) == float(lims[1]):
-                raise ValueError(MINMAX_ERROR)
+            _read_state(state, outliers=outliers)
     return out[..., None]
 
 
@@ -566,9 +585,7 @@ def prepare_imaging(raw, preprocess='rsom', lower_thresh: float = 0.05, upper_th
 def _value_mode_into(x: torch.Tensor, mm_ptr, result: torch.Tensor) -> None:
     """result (4 int32 words on the device) = vg_value_mode of x, of its min-max normalisation when mm_ptr names a vg_minmax row."""
     n = x.numel()
-    nbytes = int(lib.vg_value_mode_scratch_bytes(n))
-    _check(nbytes, 'vg_value_mode_scratch_bytes')
-    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
+    scratch, nbytes = _scratch('vg_value_mode_scratch_bytes', n, dev=x.device)
     _check(lib.vg_value_mode(_p(x), n, mm_ptr, _p(result), _p(scratch), nbytes, stream()), 'vg_value_mode')
 
 
@@ -615,12 +632,12 @@ def prepare_segmentation(raw, check: bool = True, device=None, target_size=None,
     _mode_count_ok(math.prod(v.shape if tgt is None else tgt), 'prepare_segmentation')
     dev = v.buf.device
     with torch.cuda.device(dev):
-        state = torch.zeros(8, dtype=torch.int32, device=dev)       # [0] non-finite counter, [1..7] written by vg_label_finish
-        x = _to_f32(v, _p(state))                                   # ours: everything below runs in place
+        state = _state_block(dev, 8)                                # [0] non-finite counter, [1..7] written by vg_label_finish
+        x = _to_f32(v, _word(state, W_NONFINITE))                   # ours: everything below runs in place
         if tgt is not None:
             x = _resize_f32(x, tgt)
             n = x.numel()
-            _check(lib.vg_clip_rescale(_p(x), n, _p(_label_clamp_stats(dev)), 0.0, 0.0, 0, _p(state) + 8, _p(x), stream()), 'vg_clip_rescale')
+            _check(lib.vg_clip_rescale(_p(x), n, _p(_label_clamp_stats(dev)), 0.0, 0.0, 0, _word(state, W_LO), _p(x), stream()), 'vg_clip_rescale')
         n = x.numel()
         mm = torch.zeros(1, 4, device=dev)
         _check(lib.vg_minmax(_p(x), 1, n, _p(mm), stream()), 'vg_minmax')
@@ -629,16 +646,10 @@ def prepare_segmentation(raw, check: bool = True, device=None, target_size=None,
         _check(lib.vg_label_finish(_p(x), n, _p(mm), _p(result), _p(x), _p(state), stream()), 'vg_label_finish')
         info = None
         if check or return_info:
-            host = state.cpu()
-            lims = host[2:4].view(torch.float32)
-            if check:
-                if int(host[0]) != 0:
-                    raise ValueError('NaN detected')
-                if float(lims[0]) == float(lims[1]):
-                    raise ValueError(MINMAX_ERROR)
-                if int(host[6]) != 0:
-                    raise RuntimeError('vg_value_mode reported status %d' % int(host[6]))
-            info = dict(inverted=bool(int(host[1])), mode=float(host[4:5].view(torch.float32)[0]), count=int(host[5]),
-                        min=float(lims[0]), max=float(lims[1]))
+            host, lo, hi = _read_state(state, check)
+            if check and int(host[W_MODE_STATUS]) != 0:
+                raise RuntimeError('vg_value_mode reported status %d' % int(host[W_MODE_STATUS]))
+            info = dict(inverted=bool(int(host[W_INVERTED])), mode=float(host[W_MODE:W_MODE + 1].view(torch.float32)[0]),
+                        count=int(host[W_MODE_COUNT]), min=lo, max=hi)
     out = x[..., None]
     return (out, info) if return_info else out
