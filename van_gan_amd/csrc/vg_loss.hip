@@ -346,22 +346,43 @@ __device__ __forceinline__ void gauss3(float* g) {
 }
 #define SSIM_C1 1e-4f
 #define SSIM_C2 9e-4f
-__global__ void ssim_fwd_kernel(const float* t, const float* p, int B, int D, int H, int W, float* acc, float* part) {
+__global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* t, const float* p, int B, int D, int H, int W, float* acc, float* part) {
     __shared__ float sm[4];
     float g[3]; gauss3(g);
     const int64_t S = (int64_t)D * H * W, total = (int64_t)B * S;
     float loss = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int w = (int)(i % W); int64_t r = i / W; const int h = (int)(r % H); r /= H; const int d = (int)(r % D); const int b = (int)(r / D);
-        float mt = 0.f, mp = 0.f, ett = 0.f, epp = 0.f, etp = 0.f;
-        for (int a = -1; a <= 1; ++a) { const int dd = d + a; if (dd < 0 || dd >= D) continue;
-            for (int c = -1; c <= 1; ++c) { const int hh = h + c; if (hh < 0 || hh >= H) continue;
-                for (int e = -1; e <= 1; ++e) { const int ww = w + e; if (ww < 0 || ww >= W) continue;
-                    const float wt = g[a + 1] * g[c + 1] * g[e + 1];
-                    const size_t j = (size_t)b * S + ((size_t)dd * H + hh) * W + ww;
-                    const float tv = t[j], pv = p[j];
-                    mt += wt * tv; mp += wt * pv; ett += wt * tv * tv; epp += wt * pv * pv; etp += wt * tv * pv;
+        // the 27 window voxels of both volumes are requested on addresses clamped into the sample's volume, none behind a branch (a load
+        // behind `continue` is waited for before the next one leaves: nine dependent round trips per voxel); the padding is applied
+        // afterwards by skipping the same terms as before, in the same order
+        float tv[27], pv[27];
+        unsigned inside = 0;
+        const float* tb = t + (size_t)b * S; const float* pb = p + (size_t)b * S;
+#pragma unroll
+        for (int a = -1; a <= 1; ++a) { const int dd = d + a, cd = min(max(dd, 0), D - 1);
+#pragma unroll
+            for (int c = -1; c <= 1; ++c) { const int hh = h + c, ch = min(max(hh, 0), H - 1);
+#pragma unroll
+                for (int e = -1; e <= 1; ++e) { const int ww = w + e, cw = min(max(ww, 0), W - 1);
+                    const int k = ((a + 1) * 3 + (c + 1)) * 3 + (e + 1);
+                    const size_t j = ((size_t)cd * H + ch) * W + cw;
+                    tv[k] = ld_global(tb + j); pv[k] = ld_global(pb + j);
+                    inside |= (unsigned)((cd == dd) & (ch == hh) & (cw == ww)) << k;
                 } } }
+        float mt = 0.f, mp = 0.f, ett = 0.f, epp = 0.f, etp = 0.f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int e = 0; e < 3; ++e) {
+                    const int k = (a * 3 + c) * 3 + e;
+                    const bool in = (inside >> k) & 1;                 // (selects, not a branch: a load would be moved behind it)
+                    const float wt = g[a] * g[c] * g[e];
+                    mt = in ? mt + wt * tv[k] : mt; mp = in ? mp + wt * pv[k] : mp;
+                    ett = in ? ett + wt * tv[k] * tv[k] : ett; epp = in ? epp + wt * pv[k] * pv[k] : epp; etp = in ? etp + wt * tv[k] * pv[k] : etp;
+                }
         const float stt = ett - mt * mt, spp = epp - mp * mp, stp = etp - mt * mp;
         const float A = 2.f * mt * mp + SSIM_C1, Bq = 2.f * stp + SSIM_C2;
         const float Cq = mt * mt + mp * mp + SSIM_C1, Dq = stt + spp + SSIM_C2;
@@ -386,22 +407,42 @@ extern "C" int vg_ssim_fwd(const float* t, const float* p, int B, int D, int H, 
     hipLaunchKernelGGL(ssim_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, p, B, D, H, W, acc, part);
     return vg_check_launch();
 }
-__global__ void ssim_bwd_kernel(const float* t, const float* p, const float* part, int B, int D, int H, int W, float gscale,
+__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* t, const float* p, const float* part, int B, int D, int H, int W, float gscale,
                                 float* gp, int accum) {
     float g[3]; gauss3(g);
     const int64_t S = (int64_t)D * H * W, total = (int64_t)B * S;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int w = (int)(i % W); int64_t r = i / W; const int h = (int)(r % H); r /= H; const int d = (int)(r % D); const int b = (int)(r / D);
-        float f0 = 0.f, f1 = 0.f, f2 = 0.f;
-        for (int a = -1; a <= 1; ++a) { const int dd = d + a; if (dd < 0 || dd >= D) continue;
-            for (int c = -1; c <= 1; ++c) { const int hh = h + c; if (hh < 0 || hh >= H) continue;
-                for (int e = -1; e <= 1; ++e) { const int ww = w + e; if (ww < 0 || ww >= W) continue;
-                    const float wt = g[a + 1] * g[c + 1] * g[e + 1];
-                    const size_t j = (size_t)b * S + ((size_t)dd * H + hh) * W + ww;
-                    f0 += wt * part[j]; f1 += wt * part[total + j]; f2 += wt * part[2 * total + j];
+        // as in ssim_fwd_kernel: every operand requested on a clamped address before the first wait, the padding applied afterwards
+        float q0[27], q1[27], q2[27];
+        unsigned inside = 0;
+        const float* pb = part + (size_t)b * S;
+#pragma unroll
+        for (int a = -1; a <= 1; ++a) { const int dd = d + a, cd = min(max(dd, 0), D - 1);
+#pragma unroll
+            for (int c = -1; c <= 1; ++c) { const int hh = h + c, ch = min(max(hh, 0), H - 1);
+#pragma unroll
+                for (int e = -1; e <= 1; ++e) { const int ww = w + e, cw = min(max(ww, 0), W - 1);
+                    const int k = ((a + 1) * 3 + (c + 1)) * 3 + (e + 1);
+                    const size_t j = ((size_t)cd * H + ch) * W + cw;
+                    q0[k] = ld_global(pb + j); q1[k] = ld_global(pb + total + j); q2[k] = ld_global(pb + 2 * total + j);
+                    inside |= (unsigned)((cd == dd) & (ch == hh) & (cw == ww)) << k;
                 } } }
-        const float v = gscale * (f0 + 2.f * p[i] * f1 + t[i] * f2);
-        gp[i] = accum ? gp[i] + v : v;
+        const float pi = ld_global(p + i), ti = ld_global(t + i), old = ld_global(gp + i);      // (old is used when accumulating only)
+        float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int e = 0; e < 3; ++e) {
+                    const int k = (a * 3 + c) * 3 + e;
+                    const bool in = (inside >> k) & 1;
+                    const float wt = g[a] * g[c] * g[e];
+                    f0 = in ? f0 + wt * q0[k] : f0; f1 = in ? f1 + wt * q1[k] : f1; f2 = in ? f2 + wt * q2[k] : f2;
+                }
+        const float v = gscale * (f0 + 2.f * pi * f1 + ti * f2);
+        gp[i] = accum ? old + v : v;
     }
 }
 extern "C" int vg_ssim_bwd(const float* t, const float* p, const float* part, int B, int D, int H, int W, float gscale,
@@ -429,6 +470,91 @@ extern "C" int vg_ssim_bwd(const float* t, const float* p, const float* part, in
 #define SK_TW 32
 #define SK_TH 8
 #define SK_TD 8
+// ---- two-phase tile loader.  A bounds-checked `v = in[...]` in a loop compiles to one load behind a branch and a full wait per
+// element: a 256-thread block then makes ceil(NH / 256) = 14 dependent round trips for its 3 400-element halo, and the launch lasts
+// as long as those round trips, whatever it computes.  So: REQUEST every element on an address clamped into the sample's own volume
+// (always a valid address, no branch between two loads -- they leave back to back) and remember which were inside; COMMIT
+// `inside ? v : fill` to LDS afterwards.  E = halo width (1 for the single steps, K for K erosions per launch).
+// Which thread takes which element: a halo plane has P = XH * XW elements.  The first 256 * FP of every plane go to the threads in
+// FP full passes (part A: a thread's in-plane offset is the same in every plane and the plane's offset is the same for every thread,
+// so the addresses cost two registers, not two per element -- skel_chain_kernel keeps a whole tile in flight across its walk); the
+// rests of R elements per plane are taken together, ceil(XD * R / 256) passes (part B).  14 loads per thread for E = 1 either way.
+template <int E> struct SkHalo {
+    static constexpr int XD = SK_TD + 2 * E, XH = SK_TH + 2 * E, XW = SK_TW + 2 * E;
+    static constexpr int P = XH * XW, FP = P / 256, R = P % 256, NA = XD * FP, NB = (XD * R + 255) / 256;
+    static constexpr int N = XD * P, NR = NA + NB;
+    static_assert(FP >= 1 && FP <= 4 && R > 0 && NB <= 12 && XD <= 16, "bit layout of the inside mask");
+    // inside mask: bits 0..3 part A's in-plane predicate per pass, bits 4..15 part B's elements, bits 16..31 plane z inside [0, D)
+    // halo-linear index (= LDS index) of register k.  Part B's last pass is ragged: its spare threads repeat the last element.
+    static __device__ __forceinline__ int index(int k, int tid) {
+        if (k < NA) return (k / FP) * P + tid + 256 * (k % FP);
+        const int i = min(tid + 256 * (k - NA), XD * R - 1);
+        const int z = i / R;
+        return z * P + 256 * FP + (i - z * R);
+    }
+    static __device__ __forceinline__ bool inside(uint32_t mask, int k) {
+        if (k < NA) return (mask >> (k % FP)) & (mask >> (16 + k / FP)) & 1;
+        return (mask >> (4 + k - NA)) & 1;
+    }
+};
+// a block-uniform pointer, pinned to scalar registers: `uniform + per-thread offset` stays one add per load and is not re-associated
+// into a vector address per plane that lives through the whole kernel
+__device__ __forceinline__ const float* sk_uniform(const float* p) {
+    const uint64_t a = (uint64_t)(uintptr_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return (const float*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+template <int E>
+__device__ __forceinline__ uint32_t sk_halo_request(float (&v)[SkHalo<E>::NR], const float* __restrict__ in, size_t vol,
+                                                    int w0, int h0, int d0, int D, int H, int W, int tid) {
+    using G = SkHalo<E>;
+    const float* base = in + vol;
+    uint32_t mask = 0;                                            // (no && below: a branch would stand between two loads)
+    size_t offA[G::FP];
+#pragma unroll
+    for (int q = 0; q < G::FP; ++q) {
+        const int e = tid + 256 * q;
+        const int y = e / G::XW, x = e - y * G::XW;
+        const int gw = w0 - E + x, gh = h0 - E + y;
+        const int cw = min(max(gw, 0), W - 1), ch = min(max(gh, 0), H - 1);
+        mask |= (uint32_t)((cw == gw) & (ch == gh)) << q;
+        offA[q] = (size_t)ch * W + cw;
+    }
+#pragma unroll
+    for (int z = 0; z < G::XD; ++z) {
+        const int gd = d0 - E + z, cd = min(max(gd, 0), D - 1);
+        mask |= (uint32_t)(cd == gd) << (16 + z);
+        const float* plane = sk_uniform(base + (size_t)cd * H * W);
+#pragma unroll
+        for (int q = 0; q < G::FP; ++q) v[z * G::FP + q] = ld_global(plane + offA[q]);
+    }
+#pragma unroll
+    for (int m = 0; m < G::NB; ++m) {
+        const int i = G::index(G::NA + m, tid);
+        const int x = i % G::XW; const int r = i / G::XW;
+        const int y = r % G::XH, z = r / G::XH;
+        const int gw = w0 - E + x, gh = h0 - E + y, gd = d0 - E + z;
+        const int cw = min(max(gw, 0), W - 1), ch = min(max(gh, 0), H - 1), cd = min(max(gd, 0), D - 1);
+        mask |= (uint32_t)((cw == gw) & (ch == gh) & (cd == gd)) << (4 + m);
+        v[G::NA + m] = ld_global(base + ((size_t)cd * H + ch) * W + cw);
+    }
+    return mask;
+}
+template <int E>
+__device__ __forceinline__ void sk_halo_commit(float* __restrict__ t, const float (&v)[SkHalo<E>::NR], uint32_t mask, float fill, int tid) {
+    using G = SkHalo<E>;
+    // (the ragged pass stores the repeated element again, the same value: a store behind `i < N` would take its load along, behind
+    // the branch and a full wait)
+#pragma unroll
+    for (int k = 0; k < G::NR; ++k) t[G::index(k, tid)] = G::inside(mask, k) ? v[k] : fill;
+}
+// One thread's column of SK_TD per-voxel operands (voxel (d0 + k, gh, gw)), requested the same way: in front of the barrier that
+// publishes the tile, on clamped addresses.  The caller uses v[k] only where the voxel is inside the volume.
+__device__ __forceinline__ void sk_col_request(float (&v)[SK_TD], const float* p, size_t vol, int gw, int gh, int d0, int D, int H, int W) {
+    const int cw = min(gw, W - 1), ch = min(gh, H - 1);
+#pragma unroll
+    for (int k = 0; k < SK_TD; ++k) v[k] = ld_global(p + vol + ((size_t)min(d0 + k, D - 1) * H + ch) * W + cw);
+}
 template <bool ERODE>
 __global__ __launch_bounds__(256) void skel_tile_kernel(const float* __restrict__ in, const float* __restrict__ imgj,
                                                         const float* __restrict__ prev, int D, int H, int W, float* __restrict__ out) {
@@ -441,18 +567,16 @@ __global__ __launch_bounds__(256) void skel_tile_kernel(const float* __restrict_
     const int w0 = tw * SK_TW, h0 = th * SK_TH, d0 = td * SK_TD;
     const size_t vol = (size_t)blockIdx.y * D * H * W;
     const float fill = ERODE ? INFINITY : -INFINITY;
-    constexpr int NH = (SK_TD + 2) * (SK_TH + 2) * (SK_TW + 2);
-    for (int i = tid; i < NH; i += 256) {
-        const int x = i % (SK_TW + 2); const int r = i / (SK_TW + 2);
-        const int y = r % (SK_TH + 2), z = r / (SK_TH + 2);
-        const int gw = w0 + x - 1, gh = h0 + y - 1, gd = d0 + z - 1;
-        float v = fill;
-        if (gw >= 0 && gw < W && gh >= 0 && gh < H && gd >= 0 && gd < D) v = in[vol + ((size_t)gd * H + gh) * W + gw];
-        (&t[0][0][0])[i] = v;
-    }
-    __syncthreads();
     const int tx = tid & (SK_TW - 1), ty = tid >> 5;
     const int gw = w0 + tx, gh = h0 + ty;
+    float hv[SkHalo<1>::NR], cj[SK_TD], cp[SK_TD];
+    const uint32_t inside = sk_halo_request<1>(hv, in, vol, w0, h0, d0, D, H, W, tid);
+    if (!ERODE) {                                                 // (prev == nullptr, the first step: the column is requested from imgj and not used)
+        sk_col_request(cj, imgj, vol, gw, gh, d0, D, H, W);
+        sk_col_request(cp, prev ? prev : imgj, vol, gw, gh, d0, D, H, W);
+    }
+    sk_halo_commit<1>(&t[0][0][0], hv, inside, fill, tid);
+    __syncthreads();
     float p9[3], p5[3];                       // per-slice partials of slices s-2, s-1, s (ring)
 #pragma unroll
     for (int sl = 0; sl < SK_TD + 2; ++sl) {
@@ -476,8 +600,8 @@ __global__ __launch_bounds__(256) void skel_tile_kernel(const float* __restrict_
                 const size_t o = vol + ((size_t)gd * H + gh) * W + gw;
                 if (ERODE) out[o] = nb;
                 else {
-                    const float delta = fmaxf(imgj[o] - nb, 0.f);
-                    if (prev) { const float sp = prev[o]; out[o] = sp + fmaxf(delta - sp * delta, 0.f); }
+                    const float delta = fmaxf(cj[sl - 2] - nb, 0.f);
+                    if (prev) { const float sp = cp[sl - 2]; out[o] = sp + fmaxf(delta - sp * delta, 0.f); }
                     else out[o] = delta;
                 }
             }
@@ -505,29 +629,23 @@ __global__ __launch_bounds__(256) void skel_chain_kernel(const float* __restrict
     const int th = bt % tiles_h; const int td = bt / tiles_h;
     const int w0 = tw * SK_TW, h0 = th * SK_TH, d0 = td * SK_TD;
     const size_t vol = (size_t)blockIdx.y * D * H * W;
-    constexpr int NH = (SK_TD + 2) * (SK_TH + 2) * (SK_TW + 2);
     const int tx = tid & (SK_TW - 1), ty = tid >> 5;
     const int gw = w0 + tx, gh = h0 + ty;
     const bool col_ok = gw < W && gh < H;
-    float cen[SK_TD], sk[SK_TD];
+    // !AUX: the tile of img_{j+2} is requested into registers as soon as the tile of img_{j+1} is published, and committed to the (one)
+    // LDS tile after step j's walk: a step lasts max(round trip, walk) instead of their sum.  Every step's halo has the same geometry.
+    // AUX keeps request and commit together at the top of the step: its walk has no 14 registers to spare at 4 blocks per CU.
+    float cen[SK_TD], sk[SK_TD], hv[SkHalo<1>::NR];
+    const uint32_t inside = sk_halo_request<1>(hv, imgs + n, vol, w0, h0, d0, D, H, W, tid);     // img_1
+    sk_col_request(cen, imgs, vol, gw, gh, d0, D, H, W);                                          // img_0 (used inside the volume only)
 #pragma unroll
-    for (int k = 0; k < SK_TD; ++k) {
-        const int gd = d0 + k;
-        cen[k] = (col_ok && gd < D) ? imgs[vol + ((size_t)gd * H + gh) * W + gw] : 0.f;       // img_0
-        sk[k] = 0.f;
-    }
+    for (int k = 0; k < SK_TD; ++k) sk[k] = 0.f;
     for (int j = 0; j <= iters; ++j) {
-        const float* __restrict__ in = imgs + (size_t)(j + 1) * n;
+        if (AUX && j > 0) sk_halo_request<1>(hv, imgs + (size_t)(j + 1) * n, vol, w0, h0, d0, D, H, W, tid);
         __syncthreads();                                  // the previous step's readers are done with the tile
-        for (int i = tid; i < NH; i += 256) {
-            const int x = i % (SK_TW + 2); const int r = i / (SK_TW + 2);
-            const int y = r % (SK_TH + 2), z = r / (SK_TH + 2);
-            const int qw = w0 + x - 1, qh = h0 + y - 1, qd = d0 + z - 1;
-            float v = -INFINITY;
-            if (qw >= 0 && qw < W && qh >= 0 && qh < H && qd >= 0 && qd < D) v = in[vol + ((size_t)qd * H + qh) * W + qw];
-            (&t[0][0][0])[i] = v;
-        }
+        sk_halo_commit<1>(&t[0][0][0], hv, inside, -INFINITY, tid);
         __syncthreads();
+        if (!AUX && j < iters) sk_halo_request<1>(hv, imgs + (size_t)(j + 2) * n, vol, w0, h0, d0, D, H, W, tid);   // (img_{iters+1} is the last volume)
         float* __restrict__ out = skels + (size_t)j * n;
         float p9[3]; int k9[3];
 #pragma unroll
@@ -623,17 +741,18 @@ __global__ __launch_bounds__(256) void erode_multi_kernel(const float* __restric
     const int tid = threadIdx.x;
     SK_TILE_ORIGIN()
     (void)tx; (void)ty; (void)gw; (void)gh;
-    for (int i = tid; i < XD * XH * XW; i += 256) {
-        const int x = i % XW; const int r = i / XW; const int y = r % XH, z = r / XH;
-        const int qw = w0 - K + x, qh = h0 - K + y, qd = d0 - K + z;
-        float v = INFINITY;
-        if (qw >= 0 && qw < W && qh >= 0 && qh < H && qd >= 0 && qd < D) {
-            const size_t o = vol + ((size_t)qd * H + qh) * W + qw;
-            v = in[o];
-            // the first launch of a skeleton also files its input as img_0 (the chain and the backward pass index the stored chain)
-            if (copy0 && x >= K && x < K + SK_TW && y >= K && y < K + SK_TH && z >= K && z < K + SK_TD) copy0[o] = v;
+    float hv[SkHalo<K>::NR];
+    const uint32_t inside = sk_halo_request<K>(hv, in, vol, w0, h0, d0, D, H, W, tid);
+    sk_halo_commit<K>(A, hv, inside, INFINITY, tid);
+    if (copy0) {
+        // the first launch of a skeleton also files its input as img_0 (the chain and the backward pass index the stored chain)
+#pragma unroll
+        for (int k = 0; k < SkHalo<K>::NR; ++k) {
+            const int i = SkHalo<K>::index(k, tid);
+            const int x = i % XW; const int r = i / XW; const int y = r % XH, z = r / XH;
+            if (SkHalo<K>::inside(inside, k) && x >= K && x < K + SK_TW && y >= K && y < K + SK_TH && z >= K && z < K + SK_TD)
+                copy0[vol + ((size_t)(d0 - K + z) * H + (h0 - K + y)) * W + (w0 - K + x)] = hv[k];
         }
-        A[i] = v;
     }
     __syncthreads();
     erode_stage<K - 1>(A, Bf, w0, h0, d0, D, H, W, vol, outs, tid);
@@ -657,15 +776,9 @@ static dim3 skel_grid(int B, int D, int H, int W) {
 // that order; outside the volume the tile holds +-inf, which a strict comparison never selects.
 __device__ __forceinline__ void sk_load_tile(float (&t)[SK_TD + 2][SK_TH + 2][SK_TW + 2], const float* __restrict__ in, size_t vol,
                                              int w0, int h0, int d0, int D, int H, int W, float fill, int tid) {
-    constexpr int NH = (SK_TD + 2) * (SK_TH + 2) * (SK_TW + 2);
-    for (int i = tid; i < NH; i += 256) {
-        const int x = i % (SK_TW + 2); const int r = i / (SK_TW + 2);
-        const int y = r % (SK_TH + 2), z = r / (SK_TH + 2);
-        const int gw = w0 + x - 1, gh = h0 + y - 1, gd = d0 + z - 1;
-        float v = fill;
-        if (gw >= 0 && gw < W && gh >= 0 && gh < H && gd >= 0 && gd < D) v = in[vol + ((size_t)gd * H + gh) * W + gw];
-        (&t[0][0][0])[i] = v;
-    }
+    float hv[SkHalo<1>::NR];
+    const uint32_t inside = sk_halo_request<1>(hv, in, vol, w0, h0, d0, D, H, W, tid);
+    sk_halo_commit<1>(&t[0][0][0], hv, inside, fill, tid);
 }
 // backward step j, part 1: local gradients of the skeleton update
 __global__ __launch_bounds__(256) void skel_bwd_local_kernel(const float* __restrict__ imgj, const float* __restrict__ imgj1,
@@ -674,7 +787,15 @@ __global__ __launch_bounds__(256) void skel_bwd_local_kernel(const float* __rest
     __shared__ float t[SK_TD + 2][SK_TH + 2][SK_TW + 2];
     const int tid = threadIdx.x;
     SK_TILE_ORIGIN()
-    sk_load_tile(t, imgj1, vol, w0, h0, d0, D, H, W, -INFINITY, tid);
+    // the tile and this thread's per-voxel operands are all requested before the first wait (prev == nullptr, the first step: its
+    // column is requested from imgj and not used).  dimgj[i] is read and written by this thread alone in this launch.
+    float hv[SkHalo<1>::NR], cj[SK_TD], cg[SK_TD], cp[SK_TD], ca[SK_TD];
+    const uint32_t inside = sk_halo_request<1>(hv, imgj1, vol, w0, h0, d0, D, H, W, tid);
+    sk_col_request(cj, imgj, vol, gw, gh, d0, D, H, W);
+    sk_col_request(cg, gs, vol, gw, gh, d0, D, H, W);
+    sk_col_request(cp, prev ? prev : imgj, vol, gw, gh, d0, D, H, W);
+    sk_col_request(ca, dimgj, vol, gw, gh, d0, D, H, W);
+    sk_halo_commit<1>(&t[0][0][0], hv, inside, -INFINITY, tid);
     __syncthreads();
     if (gw >= W || gh >= H) return;
     // dilation value and its FIRST arg-max (scan order a (D), b (H), c (W) ascending) by the forward kernels' column walk: the first
@@ -697,19 +818,19 @@ __global__ __launch_bounds__(256) void skel_bwd_local_kernel(const float* __rest
         float dil = m9[(sl - 2) % 3]; int code = k9[(sl - 2) % 3];
         if (m9[(sl - 1) % 3] > dil) { dil = m9[(sl - 1) % 3]; code = 9 + k9[(sl - 1) % 3]; }
         if (m9[sl % 3] > dil) { dil = m9[sl % 3]; code = 18 + k9[sl % 3]; }
-        const float raw = imgj[i] - dil;
+        const float raw = cj[sl - 2] - dil;
         const float delta = fmaxf(raw, 0.f);
-        const float g = gs[i];
+        const float g = cg[sl - 2];
         float ddelta;
         if (prev) {
-            const float sp = prev[i];
+            const float sp = cp[sl - 2];
             const float u = delta - sp * delta;
             const float dr = u > 0.f ? g : 0.f;
             ddelta = dr * (1.f - sp);
             gs[i] = g - dr * delta;             // d skel_{j-1}
         } else ddelta = g;
         const float e = raw > 0.f ? ddelta : 0.f;
-        if (e != 0.f) { dimgj[i] += e; atomicAdd(&dimgj1[(int64_t)i + sk_off(code, H, W)], -e); }
+        if (e != 0.f) { dimgj[i] = ca[sl - 2] + e; atomicAdd(&dimgj1[(int64_t)i + sk_off(code, H, W)], -e); }
     }
 }
 // part 2: d img_j += erode^T(d img_{j+1})
@@ -720,7 +841,10 @@ __global__ __launch_bounds__(256) void erode_bwd_kernel(const float* __restrict_
     __shared__ float t[SK_TD + 2][SK_TH + 2][SK_TW + 2];
     const int tid = threadIdx.x;
     SK_TILE_ORIGIN()
-    sk_load_tile(t, imgj, vol, w0, h0, d0, D, H, W, INFINITY, tid);
+    float hv[SkHalo<1>::NR], cg[SK_TD];
+    const uint32_t inside = sk_halo_request<1>(hv, imgj, vol, w0, h0, d0, D, H, W, tid);
+    sk_col_request(cg, dimgj1, vol, gw, gh, d0, D, H, W);           // (read by this thread alone; the launch only writes zeros into it)
+    sk_halo_commit<1>(&t[0][0][0], hv, inside, INFINITY, tid);
     __syncthreads();
     if (gw >= W || gh >= H) return;
     // first arg-min of the 19-voxel footprint in the reference's scan order, by the column walk of skel_erode_code_kernel
@@ -741,7 +865,7 @@ __global__ __launch_bounds__(256) void erode_bwd_kernel(const float* __restrict_
         const int gd = d0 + sl - 2;
         if (gd >= D) continue;
         const size_t i = vol + ((size_t)gd * H + gh) * W + gw;
-        const float g = dimgj1[i];
+        const float g = cg[sl - 2];
         if (g == 0.f) continue;
         dimgj1[i] = 0.f;
         const int lo = (sl - 2) % 3, c = (sl - 1) % 3, hi = sl % 3;
