@@ -729,6 +729,61 @@ int vg_volume_moments(const void* vol, int dtype, int64_t n, float* mean_std, vo
 int vg_outlier_limits(const void* vol, int dtype, int64_t n, const float* mean_std, float threshold, float* stats4,
                       uint32_t* kept_nonfinite2, vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Prediction post-processing (what a user does with the stitched prediction, 255 * minmax(pred), that stitch_subvolumes returns where the
+ * reference writes a TIFF, custom_callback.py:202-223): threshold, 3-D connected components, removal of small components;
+ * van_gan_amd/postprocess.py (binarise_prediction, label_components, remove_small_objects, vessel_mask), csrc/vg_components.hip,
+ * DESIGN.md section 3.16.  The same code in both storage builds.  Volumes are [X][Y][Z] with Z innermost, n = X * Y * Z, 1 <= n < 2^31;
+ * masks are uint8 (0 is background, anything else foreground; the entries write 0 / 1), labels are int32.  Every entry only enqueues,
+ * allocates nothing and checks its arguments on the host before any launch (VG_EINVAL, nothing launched): NULL pointers (those named
+ * _or_null excepted), n out of range, a pointer that is not aligned for its type, a scratch smaller than its query says or not 16-byte
+ * aligned, and what is listed per entry.  Only integer atomics, and every result is an integer that does not depend on their order:
+ * equal inputs give bit-identical results on every run.  No workgroup waits on another, and every loop is bounded.
+ *
+ * vg_cc_label: labels[v] = 0 where mask[v] == 0, else the number 1 .. K of v's connected component under
+ *   scipy.ndimage.generate_binary_structure(3, connectivity): connectivity 1 / 2 / 3 joins the 6 / 18 / 26 neighbours that differ by 1
+ *   along at most 1 / 2 / 3 axes.  Components are numbered in raster order of their first voxel (ascending smallest linear index), which
+ *   is scipy.ndimage.label's numbering.  sizes[k] = voxels of component k for k = 1 .. K and sizes[0] = background voxels; sizes has room
+ *   for n / 2 + 2 words (no connectivity allows more than ceil(n / 2) components); entries beyond K are left alone.
+ *   result4 = (K, status, foreground voxels, 0); status 0 is success, bit 0: a loop ran into its cap, bit 1: a parent above its child
+ *   was read -- neither can happen on intact scratch; the kernels then leave the loop, and labels / sizes are unspecified but every write
+ *   stays inside its buffer.  mask is only read.  scratch: vg_cc_scratch_bytes(n) bytes, contents irrelevant on entry.
+ *   VG_EINVAL also when ceil(X / VG_CC_TILE_X) * ceil(Y / VG_CC_TILE_Y) * ceil(Z / VG_CC_TILE_Z) * 256 >= 2^32: one 256-thread workgroup
+ *   runs per tile and a grid holds fewer than 2^32 threads, so a volume of more than 2^24 - 1 tiles -- (2^27, 1, 1), say -- is refused.
+ *   Union-find with links to the smaller index only.  Six launches whatever the data: union-find in LDS over tiles of VG_CC_TILE_X x
+ *   VG_CC_TILE_Y x VG_CC_TILE_Z voxels; links across tile faces by returning agent-scope atomic minima; roots and sizes (one atomic per
+ *   tile-local component) with the count of roots per block of 2048 voxels; a one-workgroup scan of those counts; rank = label of every
+ *   root, with its size; labels.
+ * vg_cc_filter: out[v] = labels[v] != 0 && sizes[labels[v]] >= min_size (0 / 1).  K is read from result4[0] on the device.
+ *   counts2 = (kept voxels, kept components K').  newid_or_null: room for n / 2 + 2 words; newid[k] = the number 1 .. K' of component k
+ *   among the kept ones in the same order, 0 when it is dropped (newid[0] = 0); relabel_or_null (needs newid): relabel[v] =
+ *   newid[labels[v]].  Two launches: one workgroup over sizes, one streaming pass (16-byte loads where labels, out and relabel allow).
+ *   labels, out and relabel must not overlap; 0 <= min_size.
+ * vg_hist256: hist[b] = number of finite voxels with (uint8)pred == b, the conversion being C truncation of the fp32 value -- the
+ *   reference's pred.astype('uint8') (custom_callback.py:205) -- of a value in [0, 256); a finite value below 0 counts in bin 0 and one
+ *   from 256 on in bin 255.  hist (256 words) is overwritten; *nonfinite has the number of non-finite voxels ADDED to it (zeroed by the
+ *   caller).  Bins are kept per workgroup in LDS and reach hist as one atomic per occupied bin per workgroup.  1 <= n < 2^31.
+ * vg_threshold_mask: mask[v] = as_u8 ? (uint8)pred[v] > t : pred[v] > t (0 / 1; the comparison in fp32, the conversion as above), where
+ *   t = *t_dev_or_null when that is given, else the host value t.  A non-finite voxel is background and is ADDED to *nonfinite.
+ *   otsu = 1: hist256 (the 256 words vg_hist256 wrote) must be given; one thread computes Otsu's threshold from it in fp64 -- with
+ *   h = hist and b = 0 .. 255, weight1 = cumsum(h), weight2 = cumsum(h[::-1])[::-1], mean1 = cumsum(h b) / weight1, mean2 =
+ *   (cumsum((h b)[::-1]) / weight2[::-1])[::-1], var12 = weight1[:-1] weight2[1:] (mean1[:-1] - mean2[1:])^2 evaluated left to right, every
+ *   operation rounded on its own (the sums are integers below 2^53, hence exact), var12 = 0 where a weight is 0; t = the first index of
+ *   the maximum of var12 -- writes it (as fp32) to *t_otsu, and the mask is (uint8)pred > t; as_u8, t and t_dev_or_null are ignored.
+ *   An empty or one-bin histogram gives t = 0.
+ * --------------------------------------------------------------------------------------------- */
+#define VG_CC_TILE_X 8
+#define VG_CC_TILE_Y 8
+#define VG_CC_TILE_Z 64
+int64_t vg_cc_scratch_bytes(int64_t n);
+int vg_cc_label(const uint8_t* mask, int X, int Y, int Z, int connectivity, int32_t* labels, uint32_t* sizes, uint32_t* result4,
+                void* scratch, int64_t scratch_bytes, vg_stream_t stream);
+int vg_cc_filter(const int32_t* labels, int64_t n, const uint32_t* sizes, const uint32_t* result4, uint32_t min_size, uint8_t* out,
+                 uint32_t* counts2, uint32_t* newid_or_null, int32_t* relabel_or_null, vg_stream_t stream);
+int vg_hist256(const float* pred, int64_t n, uint32_t* hist, uint32_t* nonfinite, vg_stream_t stream);
+int vg_threshold_mask(const float* pred, int64_t n, int as_u8, float t, const float* t_dev_or_null, int otsu, const uint32_t* hist256_or_null,
+                      float* t_otsu_or_null, uint8_t* mask, uint32_t* nonfinite, vg_stream_t stream);
+
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */
 int vg_memset_zero(void* p, int64_t nbytes, vg_stream_t stream);

@@ -9,3 +9,4 @@ from .vangan import NETS, RESULT_KEYS, VanGan  # noqa: F401
 from .preprocess import (lanczos4_table, median_filter, order_stats, outlier_limits, percentiles, prepare_imaging,  # noqa: F401
                          prepare_segmentation, preprocess_rsom_images, resize_volume, slice_moments, threshold_outliers, value_mode,
                          volume_moments, zscore_slices)
+from .postprocess import binarise_prediction, histogram256, label_components, remove_small_objects, vessel_mask  # noqa: F401

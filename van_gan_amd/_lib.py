@@ -148,6 +148,11 @@ _SIGS = {
     'vg_volume_moments_scratch_bytes': ([c_i64], c_i64),
     'vg_volume_moments': ([c_void_p, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p], c_int),
     'vg_outlier_limits': ([c_void_p, c_int, c_i64, c_void_p, c_float, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_cc_scratch_bytes': ([c_i64], c_i64),
+    'vg_cc_label': ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p], c_int),
+    'vg_cc_filter': ([c_void_p, c_i64, c_void_p, c_void_p, C.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_hist256': ([c_void_p, c_i64, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_threshold_mask': ([c_void_p, c_i64, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

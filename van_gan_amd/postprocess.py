@@ -1,0 +1,245 @@
+"""Prediction post-processing on MI355X: from the stitched prediction -- 255 * minmax(pred), fp32, what stitch_subvolumes returns where the
+reference's GanMonitor.stitch_subvolumes writes a TIFF (custom_callback.py:202-223) -- to a binary vascular network without leaving the
+device: a threshold (a number, or Otsu's from the 256-bin histogram of pred.astype('uint8')), 3-D connected components numbered as
+scipy.ndimage.label numbers them, and the removal of components below a voxel count (skimage.morphology.remove_small_objects).  The
+arithmetic runs in csrc/vg_components.hip (include/vangan_hip.h "Prediction post-processing"); this module owns
+buffers and checks.
+
+A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost, a contiguous torch tensor ON THE DEVICE: a prediction is fp32, a mask uint8 or bool
+(0 is background).  Arguments are checked before the device is touched (ValueError).  Every function only enqueues unless a read-back
+is asked for (return_threshold, return_sizes, return_info); a read-back raises RuntimeError on a non-zero status word of vg_cc_label."""
+from __future__ import annotations
+
+import math
+import numbers
+import operator
+from typing import Tuple
+
+import torch
+
+from ._lib import check as _check, lib
+from .ops import _p, stream
+from .preprocess import _shape3
+
+R_K, R_STATUS, R_FOREGROUND = 0, 1, 2      # the words of vg_cc_label's result4
+OTSU = 'otsu'
+
+
+TILE = (8, 8, 64)                          # VG_CC_TILE_X / _Y / _Z
+MAX_TILES = (2 ** 32 - 1) // 256           # vg_cc_label runs one 256-thread workgroup per tile, and a grid holds fewer than 2^32 threads
+
+
+def label_tiles(shape) -> int:
+    """The tiles vg_cc_label cuts a volume of this shape into."""
+    return math.prod(-(-s // t) for s, t in zip(shape, TILE))
+
+
+def _device_volume(x, dtypes, what: str, labelled: bool = False) -> Tuple[torch.Tensor, Tuple[int, int, int]]:
+    """x and its (X, Y, Z); everything a wrong argument can be is rejected here, on the host -- type, shape, dtype, layout and size first,
+    none of which needs a device, then where the tensor lives.  labelled: the volume goes through vg_cc_label, which has a tile limit."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError('%s must be a torch tensor on the device, got %s' % (what, type(x).__name__))
+    shape = _shape3(x.shape)
+    if x.dtype not in dtypes:
+        raise ValueError('%s must be %s, got %s' % (what, ' or '.join(str(d) for d in dtypes), x.dtype))
+    if not x.is_contiguous():
+        raise ValueError('%s must be contiguous' % what)
+    if math.prod(shape) >= 2 ** 31:
+        raise ValueError('%s has %d voxels; the post-processing serves fewer than 2^31' % (what, math.prod(shape)))
+    if labelled and label_tiles(shape) > MAX_TILES:
+        raise ValueError('%s of shape %s is %d tiles of %dx%dx%d voxels; the labelling serves at most %d (a very thin volume: reshape it)'
+                         % ((what, shape, label_tiles(shape)) + TILE + (MAX_TILES,)))
+    if not x.is_cuda:
+        raise ValueError('%s must be on the device, got a tensor on %s' % (what, x.device))
+    return x.detach(), shape
+
+
+def _mask_volume(mask):
+    """A mask that is going to be labelled."""
+    m, shape = _device_volume(mask, (torch.uint8, torch.bool), 'mask', labelled=True)
+    return (m.view(torch.uint8) if m.dtype == torch.bool else m), shape
+
+
+def _connectivity(connectivity) -> int:
+    try:
+        c = operator.index(connectivity)
+    except TypeError:
+        raise ValueError('connectivity is 1, 2 or 3, got %r' % (connectivity,)) from None
+    if c not in (1, 2, 3):
+        raise ValueError('connectivity is 1, 2 or 3 (6, 18 or 26 neighbours), got %r' % (connectivity,))
+    return c
+
+
+def _min_size(min_size) -> int:
+    try:
+        m = operator.index(min_size)
+    except TypeError:
+        raise ValueError('min_size is an integer >= 0, got %r' % (min_size,)) from None
+    if m < 0:
+        raise ValueError('min_size is an integer >= 0, got %r' % (min_size,))
+    return min(m, 2 ** 32 - 1)                                      # no component has 2^31 voxels: every larger bound drops them all
+
+
+def _threshold(threshold):
+    """('otsu' | 'u8' | 'f32' | 'dev', value): an int compares uint8(pred) > t, a float pred > t (t rounded to fp32), a one-element fp32
+    device tensor pred > t with t read on the device."""
+    if isinstance(threshold, str):
+        if threshold != OTSU:
+            raise ValueError("threshold is a number, a one-element fp32 device tensor or 'otsu', got %r" % (threshold,))
+        return OTSU, None
+    if isinstance(threshold, torch.Tensor):
+        if not (threshold.is_cuda and threshold.dtype == torch.float32 and threshold.numel() == 1):
+            raise ValueError('a threshold tensor is one fp32 element on the device')
+        return 'dev', threshold
+    if isinstance(threshold, bool) or not isinstance(threshold, numbers.Real):
+        raise ValueError("threshold is a number, a one-element fp32 device tensor or 'otsu', got %r" % (threshold,))
+    if isinstance(threshold, numbers.Integral):
+        return 'u8', float(int(threshold))
+    if not math.isfinite(threshold):
+        raise ValueError('threshold must be finite, got %r' % (threshold,))
+    return 'f32', float(threshold)
+
+
+def _scratch(query: str, *args, dev) -> Tuple[torch.Tensor, int]:
+    """(buffer, bytes): the scratch an entry needs for these sizes, as its query tells (preprocess._scratch, on this module's handle)."""
+    nbytes = int(getattr(lib, query)(*args))
+    _check(nbytes, query)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def sizes_capacity(n: int) -> int:
+    """Words of a sizes (or newid) buffer: no connectivity allows more than ceil(n / 2) components, and word 0 is the background's."""
+    return n // 2 + 2
+
+
+def histogram256(pred, return_count: bool = False):
+    """np.bincount(pred.astype('uint8').ravel(), minlength=256) of the finite voxels as an int32 device tensor [256]; return_count: also
+    the one-element int32 device tensor that counts the non-finite voxels.  Enqueue-only."""
+    x, _ = _device_volume(pred, (torch.float32,), 'pred')
+    with torch.cuda.device(x.device):
+        hist = torch.empty(256, dtype=torch.int32, device=x.device)
+        counter = torch.zeros(1, dtype=torch.int32, device=x.device)
+        _check(lib.vg_hist256(_p(x), x.numel(), _p(hist), _p(counter), stream()), 'vg_hist256')
+    return (hist, counter) if return_count else hist
+
+
+def _binarise(x: torch.Tensor, shape, kind: str, value, counter: torch.Tensor):
+    """(mask, threshold): the threshold as the host's float, or as a one-element fp32 device tensor where the device holds it (Otsu's is
+    written there)."""
+    dev, n = x.device, x.numel()
+    mask = torch.empty(shape, dtype=torch.uint8, device=dev)
+    if kind == OTSU:
+        hist = torch.empty(256, dtype=torch.int32, device=dev)
+        t = torch.empty(1, device=dev)
+        skipped = torch.zeros(1, dtype=torch.int32, device=dev)          # vg_threshold_mask counts the same voxels again
+        _check(lib.vg_hist256(_p(x), n, _p(hist), _p(skipped), stream()), 'vg_hist256')
+        _check(lib.vg_threshold_mask(_p(x), n, 1, 0.0, None, 1, _p(hist), _p(t), _p(mask), _p(counter), stream()), 'vg_threshold_mask')
+    elif kind == 'dev':
+        t = value.reshape(1)
+        _check(lib.vg_threshold_mask(_p(x), n, 0, 0.0, _p(t), 0, None, None, _p(mask), _p(counter), stream()), 'vg_threshold_mask')
+    else:
+        t = value
+        _check(lib.vg_threshold_mask(_p(x), n, 1 if kind == 'u8' else 0, value, None, 0, None, None, _p(mask), _p(counter), stream()),
+               'vg_threshold_mask')
+    return mask, t
+
+
+def _t_host(t) -> float:
+    return float(t.cpu()[0]) if isinstance(t, torch.Tensor) else float(torch.tensor(t, dtype=torch.float32))
+
+
+def binarise_prediction(pred, threshold=127.5, return_threshold: bool = False):
+    """uint8 mask [X,Y,Z] (0 / 1) of the fp32 prediction pred ([X,Y,Z] or [X,Y,Z,1]).  threshold: a float -- pred > t; an int --
+    pred.astype('uint8') > t, the comparison on what the reference writes to its TIFF; a one-element fp32 device tensor -- pred > t with
+    t read on the device; 'otsu' -- Otsu's threshold of the 256-bin histogram of pred.astype('uint8'), computed on the device in fp64 (the
+    first maximiser of the between-class variance; 0 for a one-bin histogram), then pred.astype('uint8') > t.  A non-finite voxel is
+    background.  return_threshold=True: (mask, t) with t read back as a float (a synchronising copy); otherwise enqueue-only."""
+    kind, value = _threshold(threshold)
+    x, shape = _device_volume(pred, (torch.float32,), 'pred')
+    with torch.cuda.device(x.device):
+        mask, t = _binarise(x, shape, kind, value, torch.zeros(1, dtype=torch.int32, device=x.device))
+        return (mask, _t_host(t)) if return_threshold else mask
+
+
+def _label(m: torch.Tensor, shape, c: int):
+    """(labels, sizes, result4) of the uint8 device mask m."""
+    dev, n = m.device, m.numel()
+    labels = torch.empty(shape, dtype=torch.int32, device=dev)
+    sizes = torch.empty(sizes_capacity(n), dtype=torch.int32, device=dev)
+    result = torch.empty(4, dtype=torch.int32, device=dev)
+    scratch, nbytes = _scratch('vg_cc_scratch_bytes', n, dev=dev)
+    _check(lib.vg_cc_label(_p(m), shape[0], shape[1], shape[2], c, _p(labels), _p(sizes), _p(result), _p(scratch), nbytes, stream()), 'vg_cc_label')
+    return labels, sizes, result
+
+
+def _read_result(result: torch.Tensor):
+    host = [int(w) for w in result.cpu()]
+    if host[R_STATUS] != 0:
+        raise RuntimeError('vg_cc_label reported status %d' % host[R_STATUS])
+    return host
+
+
+def label_components(mask, connectivity=1, return_sizes: bool = False):
+    """(labels, K): int32 [X,Y,Z] with 0 for background and 1 .. K for the connected components of mask under
+    scipy.ndimage.generate_binary_structure(3, connectivity), numbered as scipy.ndimage.label numbers them (raster order of the first
+    voxel), and K as a one-element int32 device tensor.  Enqueue-only.  return_sizes=True: (labels, K, sizes) with K an int and sizes the
+    int32 device tensor [K + 1] of voxel counts, sizes[0] the background's; this reads K back and raises RuntimeError on a non-zero
+    status.  Temporary device memory: 12 bytes per voxel of scratch and 2 for the sizes, beside the 4 of the labels."""
+    c = _connectivity(connectivity)
+    m, shape = _mask_volume(mask)
+    with torch.cuda.device(m.device):
+        labels, sizes, result = _label(m, shape, c)
+        if not return_sizes:
+            return labels, result[R_K:R_K + 1]
+        K = _read_result(result)[R_K]
+        return labels, K, sizes[:K + 1]
+
+
+def _filter(labels: torch.Tensor, sizes: torch.Tensor, result: torch.Tensor, min_size: int, relabel: bool = False):
+    dev, n = labels.device, labels.numel()
+    out = torch.empty(labels.shape, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    newid = torch.empty(sizes_capacity(n), dtype=torch.int32, device=dev) if relabel else None
+    renum = torch.empty(labels.shape, dtype=torch.int32, device=dev) if relabel else None
+    _check(lib.vg_cc_filter(_p(labels), n, _p(sizes), _p(result), min_size, _p(out), _p(counts), None if newid is None else _p(newid),
+                            None if renum is None else _p(renum), stream()), 'vg_cc_filter')
+    return out, counts, renum
+
+
+def remove_small_objects(mask, min_size=64, connectivity=1, return_labels: bool = False):
+    """skimage.morphology.remove_small_objects(mask, min_size, connectivity) on the device: the uint8 mask (0 / 1) of the voxels whose
+    component has at least min_size voxels.  min_size <= 1 drops nothing: the result is a copy of mask (as 0 / 1) and nothing is labelled,
+    unless the labels are asked for.  return_labels=True: (mask, labels, K') with the kept components renumbered 1 .. K' in the same raster order and K' a
+    one-element int32 device tensor.  Enqueue-only."""
+    c = _connectivity(connectivity)
+    msz = _min_size(min_size)
+    m, shape = _mask_volume(mask)
+    with torch.cuda.device(m.device):
+        if msz <= 1 and not return_labels:
+            return (m != 0).to(torch.uint8)
+        labels, sizes, result = _label(m, shape, c)
+        out, counts, renum = _filter(labels, sizes, result, msz, return_labels)
+    return (out, renum, counts[1:2]) if return_labels else out
+
+
+def vessel_mask(pred, threshold=127.5, min_size=64, connectivity=3, return_info: bool = False):
+    """binarise_prediction, label_components and remove_small_objects chained: the uint8 mask [X,Y,Z] of the vascular network in the
+    prediction.  Enqueue-only; return_info=True: (mask, dict(threshold, components, kept, voxels, kept_voxels)) -- the threshold used, the
+    components and the voxels above it, what is left of both -- read back in one synchronising step (RuntimeError on a non-zero status)."""
+    kind, value = _threshold(threshold)
+    c = _connectivity(connectivity)
+    msz = _min_size(min_size)
+    x, shape = _device_volume(pred, (torch.float32,), 'pred', labelled=True)
+    dev = x.device
+    with torch.cuda.device(dev):
+        mask, t = _binarise(x, shape, kind, value, torch.zeros(1, dtype=torch.int32, device=dev))
+        if msz <= 1 and not return_info:
+            return mask
+        labels, sizes, result = _label(mask, shape, c)
+        out, counts, _ = _filter(labels, sizes, result, msz)
+        if not return_info:
+            return out
+        host = _read_result(result)
+        kept = [int(w) for w in counts.cpu()]
+        info = dict(threshold=_t_host(t), components=host[R_K], kept=kept[1], voxels=host[R_FOREGROUND], kept_voxels=kept[0])
+    return out, info
