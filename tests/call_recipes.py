@@ -10,6 +10,9 @@ against float64 references on the device.
 The decoder blocks' fused backward launches (vg_shortcut_dgrad_concat_norm / vg_shortcut_dgrad_concat) are not taken in dry-run mode
 (ops.ConvLayer.dgrad_concat_norm / dgrad_concat): decoder_blocks() lists them explicitly per config.
 
+cases_of() is the one loop that turns walks into cases: call_cases() feeds it the three BASELINE walks, ragged_call_cases() the walks
+of layer_recipes.RAGGED_CONFIGS / RAGGED_INFER_CONFIGS (tests/test_gpu_ragged.py, tests/test_ragged_coverage.py).
+
 Helper module (no tests in here)."""
 from __future__ import annotations
 
@@ -72,11 +75,12 @@ def inference_fin_cases() -> Dict[str, dict]:
     return cases
 
 
-def decoder_blocks(cfg) -> List[dict]:
+def decoder_blocks(cfg, configs=None) -> List[dict]:
     """The decoder blocks' fused backward launches of one config: dec0-dec3 with the shortcut's c_low (upsampled source), c_skip, cout,
-    the block's level dims and the 2B samples of the generator's backward sweep (the two applications are one sweep)."""
+    the block's level dims and the 2B samples of the generator's backward sweep (the two applications are one sweep).  configs: the
+    table `cfg` is a key of (layer_recipes.CONFIGS unless given)."""
     from van_gan_amd.nets import GEN_F
-    dims, B = LR.CONFIGS[cfg]
+    dims, B = (LR.CONFIGS if configs is None else configs)[cfg]
     out = []
     for d in range(4):
         lv = tuple(n >> d for n in dims)
@@ -90,15 +94,14 @@ def _rd(regime) -> dict:
     return dict(regime)
 
 
-@functools.lru_cache(maxsize=None)
-def call_cases() -> Dict[str, dict]:
-    """case id -> {'kind', ..., 'covers': [(entry point, regime)]}.  One case per recorded InstanceNorm-backward regime (statistics then
-    apply: covers the three single-descriptor entry points), per recorded apply2 pair (statistics of both jobs, then the two-job
-    launch), per decoder block of each config (covers its vg_concat_bwd), per stem shortcut / tanh call, and per (forward variant, tail
+def cases_of(walks, configs) -> Dict[str, dict]:
+    """The case list of a set of walks ({config: (conv records, non-convolution calls)}, in order): case id -> {'kind', ..., 'covers':
+    [(entry point, regime)]}.  One case per recorded InstanceNorm-backward regime (statistics then apply: covers the three
+    single-descriptor entry points), per recorded apply2 pair (statistics of both jobs, then the two-job launch), per decoder block of
+    each config in `configs` (a train config: covers its vg_concat_bwd), per stem shortcut / tanh call, and per (forward variant, tail
     job shape): the cheapest call with that tail."""
     cases: Dict[str, dict] = {}
-    for cfg in LR.NEEDED:
-        recs, calls = all_walks()[cfg]
+    for cfg, (recs, calls) in walks.items():
         for name, reg in calls:
             if name in ANB_ENTRIES:
                 r = _rd(reg)
@@ -113,7 +116,7 @@ def call_cases() -> Dict[str, dict]:
             elif name == 'vg_stem_short_fwd' or name == 'vg_stem_short_bwd' or name == 'vg_tanh_bwd':
                 cid = '%s %s' % (name[3:], ' '.join('%s=%d' % kv for kv in reg))
                 cases.setdefault(cid, dict(kind=name[3:], regime=reg, config=cfg, covers=[(name, reg)]))
-        for blk in decoder_blocks(cfg):
+        for blk in (decoder_blocks(cfg, configs) if cfg in configs else []):
             cid = 'decoder %s %s' % (blk['block'], cfg)
             reg = (('N', blk['N']), ('D', blk['dims'][0]), ('H', blk['dims'][1]), ('W', blk['dims'][2]), ('Cu', blk['c_low']),
                    ('Cs', blk['c_skip']), ('has_dskip', 1), ('f32', 0))
@@ -128,6 +131,35 @@ def call_cases() -> Dict[str, dict]:
             if cid not in cases or m < cases[cid]['macs']:
                 cases[cid] = dict(kind='fin', recipe=r, variant=v, config=cfg, layer=layer, macs=m, covers=[('fin',) + key])
     return cases
+
+
+@functools.lru_cache(maxsize=None)
+def call_cases() -> Dict[str, dict]:
+    """cases_of the train steps of BASELINE configs 2, 3 and 4: what tests/test_gpu_calls.py replays."""
+    return cases_of({cfg: all_walks()[cfg] for cfg in LR.NEEDED}, {cfg: LR.CONFIGS[cfg] for cfg in LR.NEEDED})
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# ragged patches (layer_recipes.RAGGED_CONFIGS / RAGGED_INFER_CONFIGS)
+# ----------------------------------------------------------------------------------------------------------------------
+def ragged_needed_calls():
+    """Every (entry point, regime) the ragged walks record, train and inference."""
+    return sorted({c for _, calls in LR.all_ragged_walks().values() for c in calls}, key=repr)
+
+
+def ragged_needed_fin():
+    """Every (forward variant, tail job shape) the ragged walks record, train and inference."""
+    return sorted({(v, fin_shape(r)) for recs, _ in LR.all_ragged_walks().values() for k, _, v, r in recs if k == 'fwd' and r.get('fin')})
+
+
+@functools.lru_cache(maxsize=None)
+def ragged_call_cases() -> Dict[str, dict]:
+    """cases_of the ragged walks.  A non-convolution case is dropped only if every (entry point, regime) it covers is, field for field,
+    one call_cases() covers (regimes carry N and the grid, so that is the exception).  A tail case is never dropped: its key has no
+    grid in it, and the recorded call -- the voxel count of the statistics and the kernel's last, partial tiles -- is a ragged one."""
+    have = {c for case in call_cases().values() for c in case['covers']}
+    cases = cases_of(LR.all_ragged_walks(), LR.RAGGED_CONFIGS)
+    return {cid: c for cid, c in cases.items() if c['kind'] == 'fin' or not all(cv in have for cv in c['covers'])}
 
 
 def fin_stress_cases() -> Dict[str, dict]:

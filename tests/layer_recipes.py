@@ -6,7 +6,9 @@ launching and reports the kernel variant it selected (template arguments + run-t
 vg_conv3d_variant), together with a shape-level recipe of the call.  For every variant the cheapest call that selects it
 becomes its representative; tests/test_gpu_layers.py replays the representative on the GPU with random contents and
 compares it with the oracle's convolution (autograd for the two gradients), tests/test_variant_coverage.py (CPU) proves the
-representatives cover every variant of BASELINE configs 2, 3 and 4.
+representatives cover every variant of BASELINE configs 2, 3 and 4.  The same for the sliding-window inference forward
+(INFER_CONFIGS; tests/test_gpu_infer_layers.py) and for patches whose level grids are no powers of two (RAGGED_CONFIGS /
+RAGGED_INFER_CONFIGS; tests/test_gpu_ragged.py, tests/test_ragged_coverage.py).
 
 Helper module (no tests in here)."""
 from __future__ import annotations
@@ -231,6 +233,108 @@ def inference_only_variants():
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# ragged patches: legal patch sizes (axes multiples of 16, at least 32) whose level grids are no powers of two
+# ----------------------------------------------------------------------------------------------------------------------
+# 32x48x80 is the smallest legal patch with three different axes (level grids 16x24x40, 8x12x20, 4x6x10, bridge 2x3x5); 48x80x96 has no
+# power-of-two axis (24x40x48, 12x20x24, 6x10x12, bridge 3x5x6).  Batch 2 changes the dispatch of the first.  Nothing above this line
+# depends on these: CONFIGS / INFER_CONFIGS and the case lists derived from them stay what they are.
+RAGGED_CONFIGS = {
+    '32x48x80 B1': ((32, 48, 80), 1),
+    '32x48x80 B2': ((32, 48, 80), 2),
+    '48x80x96 B1': ((48, 80, 96), 1),
+}
+RAGGED_INFER_CONFIGS = {
+    'infer 32x48x80 N2': ((32, 48, 80), 2),
+    'infer 48x80x96 N2': ((48, 80, 96), 2),
+    'infer 48x80x96 N1': ((48, 80, 96), 1),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def all_ragged_walks():
+    """config -> (conv records, non-convolution calls): the train walks of RAGGED_CONFIGS, then the inference walks of RAGGED_INFER_CONFIGS."""
+    walks = {name: walk_config(dims, B) for name, (dims, B) in RAGGED_CONFIGS.items()}
+    walks.update({name: walk_inference(dims, N) for name, (dims, N) in RAGGED_INFER_CONFIGS.items()})
+    return walks
+
+
+def _cheapest(walks, keep=lambda kind, variant: True):
+    best: Dict[Tuple[str, str], dict] = {}
+    for cfg, (recs, _) in walks.items():
+        for kind, name, variant, recipe in recs:
+            key, m = (kind, variant), recipe_macs(recipe)
+            if keep(kind, variant) and (key not in best or m < best[key]['macs']):
+                best[key] = dict(recipe=recipe, config=cfg, layer=name, macs=m)
+    return best
+
+
+@functools.lru_cache(maxsize=None)
+def ragged_representatives() -> Dict[Tuple[str, str], dict]:
+    """(kind, variant) -> {'recipe', 'config', 'layer', 'macs'} for every variant of the ragged walks: the cheapest call OF A RAGGED WALK
+    that selects it, replayed as recorded (never a power-of-two call that shares the string, never shrunk: the partial tiles of the
+    recorded grid are what the case is for)."""
+    return _cheapest(all_ragged_walks())
+
+
+@functools.lru_cache(maxsize=None)
+def ragged_inference_representatives() -> Dict[Tuple[str, str], dict]:
+    """The same for the forward variants of the ragged INFERENCE walks alone, each from one of those walks (the fp16 library's cases)."""
+    return _cheapest({cfg: w for cfg, w in all_ragged_walks().items() if cfg in RAGGED_INFER_CONFIGS})
+
+
+def ragged_only_variants():
+    """The (kind, variant) pairs of the ragged walks that neither representatives() nor inference_representatives() has a case for."""
+    have = set(representatives()) | set(inference_representatives())
+    return sorted(kv for kv in ragged_representatives() if kv not in have)
+
+
+def replay_variant(recipe) -> str:
+    """recipe_variant for all three kinds: the variant the call that run_recipe rebuilds from `recipe` selects, by a CPU dry run on empty
+    tensors (a data gradient may be issued in several launches of one variant: the set must have one element)."""
+    from van_gan_amd import ops
+    kind, L = recipe['kind'], recipe['layer']
+    if kind == 'fwd':
+        return recipe_variant(recipe)
+    _, lay = make_layer_from(L, 'cpu')
+    e = lambda *shp, dt=torch.bfloat16: torch.empty(*shp, dtype=dt)
+    if kind == 'wgrad':
+        sr = recipe['src']
+        N, dims, c0, c1, sh = sr['N'], tuple(sr['dims']), sr['c0'], sr['c1'], sr['shift0']
+        src = ops.Src(e(N, *[n >> sh for n in dims], c0, dt=torch.float32 if sr['f32'] else torch.bfloat16), (N,) + dims, c0,
+                      e(N, *dims, c1) if c1 else None, c1, shift0=sh, f32=sr['f32'],
+                      scale=e(N, c0 + c1, dt=torch.float32) if sr['affine'] else None, shift=e(N, c0 + c1, dt=torch.float32) if sr['affine'] else None,
+                      act=sr['act'], noise=e(N, *[n + 2 * sr['noise_pad'] for n in dims], c0 + c1) if sr['noise'] else None, noise_pad=sr['noise_pad'])
+        dy = e(N, *lay.out_dims, L['cout'], dt=torch.float32 if recipe['dy_f32'] else torch.bfloat16)
+        got = dry_variants(lambda: lay.wgrad(src, dy))
+    else:
+        N, Cc = recipe['N'], L['cin']
+        dy = e(N, *lay.out_dims, L['cout'], dt=torch.float32 if recipe['dy_f32'] else torch.bfloat16)
+        dp = e(N, *lay.buf_dims, Cc, dt=torch.float32 if recipe['out_f32'] else torch.bfloat16)
+        bs, bdesc = recipe.get('bstat'), None
+        if bs:
+            dims_in = tuple(lay.in_dims)
+            c0, sh = (bs['c_x0'], 1) if bs['cat'] else (Cc, 0)
+            f = lambda *shp: e(*shp, dt=torch.float32)
+            bdesc = ops.actnorm_desc(dp, bs['pad'], e(N, *[n >> sh for n in dims_in], c0), (N,) + dims_in, Cc, e(N, *dims_in, Cc), scale=f(N, Cc),
+                                     shift=f(N, Cc), act=bs['act'], norm=True, gamma=f(Cc), mean=f(N, Cc), rstd=f(N, Cc),
+                                     red=f(ops.STRIPES * N * Cc * 2 + 4), accumulate=False, x1=e(N, *dims_in, Cc - c0) if bs['cat'] else None,
+                                     c_x0=c0 if bs['cat'] else 0, x0_shift=sh, dgamma=f(Cc), dbeta=f(Cc))
+        got = dry_variants(lambda: lay.dgrad(dy, N, dp, accumulate=recipe['accumulate'], bstat=bdesc))
+    assert len(set(got)) == 1, got
+    return got[0]
+
+
+def out_grid(recipe) -> Tuple[int, int, int]:
+    """The grid a recorded call's kernel tiles: the convolution's output grid (forward; weight gradient: its reduction runs over it), the
+    layer's input grid for the data gradient it writes (without the margin of a 'reflect' layer: n + 2 is never a power of two)."""
+    L = recipe['layer']
+    if recipe['kind'] == 'dgrad':
+        return tuple(L['in_dims'])
+    s, k = L['stride'], L['k']
+    return tuple((n + 2 - k) // s + 1 if L['pad'] == 'reflect' else -(-n // s) for n in L['in_dims'])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # replaying a recipe on the GPU against the CPU oracle
 # ----------------------------------------------------------------------------------------------------------------------
 def bf(x, storage=torch.bfloat16):
@@ -341,7 +445,7 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
     rounding of the stored output differ.
     storage=torch.float16 (forward calls only, made inside ops.Fp16()): 16-bit tensors are IEEE half, the reference rounds with
     .half() where it rounds to bf16 otherwise, bounds FWD_TOL[torch.float16]; a single-channel fp32 residual (res_c1, stem.cb) is
-    replayed as recorded.  Returns the measured errors of a forward replay."""
+    replayed as recorded.  Returns the measured errors of the replay."""
     from oracle import vangan_oracle as O
     L = recipe['layer']
     kind, pad, stride = recipe['kind'], L['pad'], L['stride']
@@ -405,10 +509,12 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
         torch.cuda.synchronize()
         w = w_ref.clone().requires_grad_(True)
         (O.conv3d(ap, w, None, stride, conv_pad) * dy_ref).sum().backward()
-        assert rel_l2(st.grad('c.w'), w.grad) < 2e-3, 'weight gradient rel %.2e' % rel_l2(st.grad('c.w'), w.grad)
+        err = dict(w=rel_l2(st.grad('c.w'), w.grad))
+        assert err['w'] < 2e-3, 'weight gradient rel %.2e' % err['w']
         if L['bias']:
-            assert rel_l2(st.grad('c.b'), dy_ref.sum(dim=(0, 2, 3, 4))) < 2e-3, 'bias gradient'
-        return
+            err['b'] = rel_l2(st.grad('c.b'), dy_ref.sum(dim=(0, 2, 3, 4)))
+            assert err['b'] < 2e-3, 'bias gradient rel %.2e' % err['b']
+        return err
     # data gradient: on the reflect-PADDED grid for 'reflect' convs (the fold is a separate kernel), plain grid for 'same'
     N = recipe['N']
     odt = torch.float32 if recipe['out_f32'] else torch.bfloat16
@@ -472,6 +578,7 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
     if prior is not None:
         ref = ref + prior.to(dt)
     close_bf16(dp, ref, 'data gradient', rel=2.5e-2, floor=6e-3)
+    return dict(dx=float((dp.double().cpu() - ref.double()).abs().max() / ref.double().abs().max()))
 
 
 def stress_recipe(recipe, expect_variant, dev, launches=200, seed=3):

@@ -167,11 +167,9 @@ def _stem_bwd(N, S, C_, dev, seed=22):
     return err
 
 
-@pytest.mark.parametrize('cid', _IDS)
-def test_recorded_call_matches_float64(cid):
+def run_case(c, cid, dev):
+    """One case of call_recipes.cases_of on the device (tests/test_gpu_ragged.py runs its own list through here too)."""
     from van_gan_amd import ops
-    c = _CASES[cid]
-    dev = _dev()
     kind = c['kind']
     if kind == 'anb':
         err = CR.run_anb(dict(c['regime']), dev, name=cid)
@@ -200,6 +198,12 @@ def test_recorded_call_matches_float64(cid):
         err = dict(dpre=LR.rel_l2(dp, dy.double() * (1 - y.double() ** 2)))
         assert err['dpre'] <= 1e-6
     _report(cid, err)
+    return err
+
+
+@pytest.mark.parametrize('cid', _IDS)
+def test_recorded_call_matches_float64(cid):
+    run_case(_CASES[cid], cid, _dev())
 
 
 @pytest.mark.parametrize('fam', sorted(CR.fin_stress_cases()))

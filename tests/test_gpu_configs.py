@@ -5,6 +5,8 @@
   config 4  128^3, batch 1 per GPU     full-size properties (the kernels it selects are compared with the oracle one by one at
                                        true layer shapes in tests/test_gpu_layers.py)
   config 5  256x256x128 sliding window product precision (bf16) through the stitch oracle driven by the HIP generator itself
+  ragged    32x48x80, batch 1          a legal patch no tile divides: fixture train_step_32x48x80_b1.npz; 48x80x96, batch 1 (no
+                                       power-of-two axis): full-size properties (layer by layer: tests/test_gpu_ragged.py)
 
 Full-size properties: finite losses, bf16 engine vs exact-parity (fp32 storage) engine on the same weights and inputs within
 the bf16 tolerance of tests/test_gpu_nets.py (3e-2), workspace peak constant from the second step on.
@@ -29,7 +31,7 @@ def _cos(a, b):
     return float((a * b).sum() / (a.norm() * b.norm() + 1e-300))
 
 
-@pytest.mark.parametrize('fixture', ['train_step_64_b2', 'train_step_64x64x32_b2'])
+@pytest.mark.parametrize('fixture', ['train_step_64_b2', 'train_step_64x64x32_b2', 'train_step_32x48x80_b1'])
 def test_train_step_matches_fixture(fixture):
     from van_gan_amd import VanGan
     f = np.load(os.path.join(GOLD, fixture + '.npz'))
@@ -55,7 +57,8 @@ def test_train_step_matches_fixture(fixture):
         assert c > 0.9995 and rl < 5e-2, key
 
 
-@pytest.mark.parametrize('dims,B', [((128, 128, 64), 2), ((128, 128, 128), 1)], ids=['config3 128x128x64 b2', 'config4 128^3 b1'])
+@pytest.mark.parametrize('dims,B', [((128, 128, 64), 2), ((128, 128, 128), 1), ((48, 80, 96), 1)],
+                         ids=['config3 128x128x64 b2', 'config4 128^3 b1', 'ragged 48x80x96 b1'])
 def test_full_size_properties(dims, B):
     from van_gan_amd import VanGan
     rI, rS = O.synth_volumes(B, *dims, seed=77)

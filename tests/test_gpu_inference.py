@@ -34,6 +34,60 @@ def test_stitch_subvolumes_matches_oracle(process_img):
     assert err < 0.05
 
 
+@pytest.mark.parametrize('precision', ['bf16', 'fp16'])
+def test_stitch_subvolumes_with_a_ragged_window(precision):
+    """A 32x48x80 window (level grids 16x24x40 ... 2x3x5: no tile divides them) over a 40x56x88 volume: 3 x 3 x 3 = 27 windows, two per
+    batch, so the last batch is the ONE-window forward, which dispatches differently from the two-window one
+    (layer_recipes.RAGGED_INFER_CONFIGS).  Against oracle/stitch_oracle.py, at the bounds of the existing cases:
+      bf16  the stitch oracle driven window by window by the SAME bf16 HIP generator: rel L2 < 4e-2, mean |err| < 2.0 on the 0..255 scale
+            (tests/test_gpu_configs.py, config 5: the bf16 generator's noise floor between batch compositions);
+      fp16  the stitch oracle driven by the float32 ORACLE generator on the same weights: the fp32-storage engine within 0.05 of it (the
+            bound of test_stitch_subvolumes_matches_oracle), the fp16 library within rel L2 1e-2 of it (the bound of the fp16 generator
+            against the fp32 oracle below, and of config 5's fp16 stitch)."""
+    from van_gan_amd import VanGan
+    k = (32, 48, 80)
+    vol = torch.rand(40, 56, 88, 1, generator=torch.Generator().manual_seed(3)) * 2 - 1
+    kw = dict(stride=(20, 24, 40), complete=True, padFactor=0.25, process_img=True)
+    eng = VanGan(k, batch_size=2, device='cuda:0', seed=5, precision='bf16' if precision == 'bf16' else 'fp32')
+    calls = []
+    if precision == 'bf16':
+        net, ar = eng.gen_IS, eng.arena
+
+        def gen(a):
+            ar.reset()
+            x = ar.alloc((1,) + k + (1,), torch.float32)
+            y = ar.alloc((1,) + k + (1,), torch.float32)
+            x.copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)))
+            net.forward(ar, x, y, save=False)
+            torch.cuda.synchronize()
+            calls.append(1)
+            return y.cpu().numpy()
+    else:
+        P = eng.export_weights()['gen_IS']
+
+        def gen(a):
+            calls.append(1)
+            with torch.no_grad():
+                return O.resunet_forward(P, torch.from_numpy(np.ascontiguousarray(a)).float()).numpy()
+    ref = S.stitch_subvolumes(gen, vol.numpy(), (1,) + k + (1,), **kw)
+    assert len(calls) == 27 and len(calls) % 2 == 1                  # an odd window count: the tail batch holds one window
+    assert ref.shape == (40, 56, 88, 1) and not np.isnan(ref).any()
+    got = eng.stitch_subvolumes('gen_IS', vol, k, window_batch=2, **kw).cpu().numpy()
+    assert got.shape == ref.shape and np.isfinite(got).all() and got.min() == 0.0 and abs(got.max() - 255.0) < 1e-3
+    err = np.abs(got - ref)
+    rel = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
+    print('ragged stitch, %s engine: max abs err %.4f, mean %.5f (0..255 scale), rel L2 %.3e' % (eng.precision, err.max(), err.mean(), rel))
+    if precision == 'bf16':
+        assert rel < 4e-2 and err.mean() < 2.0, (rel, float(err.mean()), float(err.max()))
+        return
+    assert err.max() < 0.05
+    got16 = eng.stitch_subvolumes('gen_IS', vol, k, window_batch=2, precision='fp16', **kw).cpu().numpy()
+    rel16 = float(np.linalg.norm(got16 - ref) / np.linalg.norm(ref))
+    print('ragged stitch, fp16 library vs the fp32 oracle: rel L2 %.3e, max abs %.4f (0..255 scale)' % (rel16, float(np.abs(got16 - ref).max())))
+    assert got16.shape == ref.shape and np.isfinite(got16).all() and got16.min() == 0.0 and abs(got16.max() - 255.0) < 1e-3
+    assert rel16 < 1e-2
+
+
 def test_fp16_generator_matches_oracle_with_fp16_storage_points():
     """BASELINE config 5 names fp16: the generator's forward in libvangan_hip_h.so (IEEE half storage, fp32 accumulation) against
     the oracle with every stored tensor and the weights rounded to fp16 at the same points (q hook); and against the unrounded

@@ -296,6 +296,9 @@ __device__ __forceinline__ void stage_halo_tile(const GatherIn& g, char* halo, c
         const int oh = rtab[set + hh], ow = rtab[set + g.HH + hw];
         const bool cvalid = c < g.Cin && (oh | ow) >= 0;
         const T* pc = cvalid ? (from0 ? b0 + c : b1 + (c - g.c0)) + (oh + ow) : b0;      // invalid columns read a dummy, then zero
+        // the dummy is src0's base, so it takes src0's plane offsets: an invalid column of the concat's SECOND source (a tile that
+        // overhangs a grid it does not divide) with src1's offsets read up to a whole src1 sample behind the 4x smaller src0
+        const bool use0 = from0 || !cvalid;
         const bf16_t* pn = nullptr; bool nvalid = false;
         if (NOISE) {
             const int nh = rtab[2 * L + hh], nw = rtab[2 * L + g.HH + hw];
@@ -321,7 +324,7 @@ __device__ __forceinline__ void stage_halo_tile(const GatherIn& g, char* halo, c
                 const int qd = rd + g.npad;
                 const bool dvalid = resolve_pos(rd, g.D, g.pad_mode);          // wave-uniform
                 const int s0 = dvalid ? (rd >> sh) * dpl0 : 0, s1 = dvalid ? rd * dpl1 : 0;
-                raw_load(raw[k], pc + (from0 ? s0 : s1));
+                raw_load(raw[k], pc + (use0 ? s0 : s1));
                 ok[k] = dvalid && cvalid;
                 nok[k] = false;
                 if (NOISE) {
@@ -460,7 +463,7 @@ __device__ __forceinline__ void stage_halo_lean(const GatherIn& g, char* halo, c
         const bool cvalid = !MASK || (c < g.Cin && (oh | ow) >= 0);
         const char* pc = (from0 ? b0 + (size_t)c * esz : b1 + (size_t)(c - g.c0) * esz) + (cvalid ? oh + ow : 0);
         if (!cvalid) pc = b0;                                              // invalid columns read a dummy, then zero
-        const int* dt = rs + g.HH + g.HW + sp.hd_lo;
+        const int* dt = (cvalid ? rs : rt) + g.HH + g.HW + sp.hd_lo;       // ... inside src0: with src0's D offsets (see stage_halo_tile)
         const char* pn = nullptr; const int* ndt = nullptr; bool nvalid = false;
         if (NOISE) {
             if (noise_on) {
