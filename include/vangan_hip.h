@@ -771,7 +771,26 @@ int vg_outlier_limits(const void* vol, int dtype, int64_t n, const float* mean_s
  *   operation rounded on its own (the sums are integers below 2^53, hence exact), var12 = 0 where a weight is 0; t = the first index of
  *   the maximum of var12 -- writes it (as fp32) to *t_otsu, and the mask is (uint8)pred > t; as_u8, t and t_dev_or_null are ignored.
  *   An empty or one-bin histogram gives t = 0.
+ *
+ * Measuring the mask (csrc/vg_edt.hip; distance_transform_edt, fill_holes, vessel_radius):
+ * vg_edt: the exact Euclidean distance of every voxel to the nearest background voxel (mask[v] == 0), 0 on the background, as
+ *   scipy.ndimage.distance_transform_edt(mask, sampling).  Needs X^2 + Y^2 + Z^2 < 2^31 beside 1 <= n < 2^31 (VG_EINVAL otherwise), so
+ *   that every squared distance in voxel units is an int32.  sampling3_or_null = NULL: integer form -- squared distances in int32 by
+ *   three separable passes (along Z: (z - z')^2 to the nearest background voxel of the row; along Y, then X: min over p' of f(p') +
+ *   (p - p')^2), the sentinel 2^31 - 1 standing for "no background voxel met" and never taking part in a sum.  out_kind
+ *   VG_EDT_SQUARED_I32 writes them (int32[n]); VG_EDT_DIST_F32 writes float[n], the fp32 rounding of the fp64 square root.  A volume
+ *   without any background voxel gives 2^31 - 1 / +inf everywhere (scipy's result is not meaningful there).  sampling3 = three doubles
+ *   IN HOST MEMORY, read before the call returns: the voxel spacing along X, Y, Z, each finite and > 0; the same passes on fp64 costs
+ *   f + s_a^2 (p - p')^2, every product and sum rounded on its own, sentinel +inf; VG_EDT_DIST_F32 only.  out is 4-byte aligned.
+ *   scratch: vg_edt_scratch_bytes(X, Y, Z, weighted) bytes (two cost arrays: 8 bytes per voxel, 16 weighted), contents irrelevant.
+ *   Three launches whatever the data; no atomics; bit-identical on every run.
+ * vg_fill_holes_mark / vg_fill_holes_apply: scipy.ndimage.binary_fill_holes with its default structure, given labels = vg_cc_label of
+ *   the INVERTED mask (1 where mask is 0) at connectivity 1.  mark: zeroes flags -- n / 2 + 2 BYTES, one per possible label -- and
+ *   sets flags[l] = 1 for every label l >= 1 met on one of the six faces of the volume (plain stores of one value).  apply:
+ *   out[v] = mask[v] != 0 || !flags[labels[v]] (0 / 1); a label outside [1, n / 2 + 2) is never used as an index.  out and mask must not overlap; 16-byte loads where labels, mask and out allow.
  * --------------------------------------------------------------------------------------------- */
+#define VG_EDT_SQUARED_I32 0
+#define VG_EDT_DIST_F32 1
 #define VG_CC_TILE_X 8
 #define VG_CC_TILE_Y 8
 #define VG_CC_TILE_Z 64
@@ -783,6 +802,11 @@ int vg_cc_filter(const int32_t* labels, int64_t n, const uint32_t* sizes, const 
 int vg_hist256(const float* pred, int64_t n, uint32_t* hist, uint32_t* nonfinite, vg_stream_t stream);
 int vg_threshold_mask(const float* pred, int64_t n, int as_u8, float t, const float* t_dev_or_null, int otsu, const uint32_t* hist256_or_null,
                       float* t_otsu_or_null, uint8_t* mask, uint32_t* nonfinite, vg_stream_t stream);
+int64_t vg_edt_scratch_bytes(int X, int Y, int Z, int weighted);
+int vg_edt(const uint8_t* mask, int X, int Y, int Z, const double* sampling3_or_null, void* out, int out_kind, void* scratch,
+           int64_t scratch_bytes, vg_stream_t stream);
+int vg_fill_holes_mark(const int32_t* labels, int X, int Y, int Z, uint8_t* flags, vg_stream_t stream);
+int vg_fill_holes_apply(const uint8_t* mask, const int32_t* labels, const uint8_t* flags, int64_t n, uint8_t* out, vg_stream_t stream);
 
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */

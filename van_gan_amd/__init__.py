@@ -10,3 +10,4 @@ from .preprocess import (lanczos4_table, median_filter, order_stats, outlier_lim
                          prepare_segmentation, preprocess_rsom_images, resize_volume, slice_moments, threshold_outliers, value_mode,
                          volume_moments, zscore_slices)
 from .postprocess import binarise_prediction, histogram256, label_components, remove_small_objects, vessel_mask  # noqa: F401
+from .postprocess import distance_transform_edt, fill_holes, vessel_radius  # noqa: F401

@@ -153,6 +153,10 @@ _SIGS = {
     'vg_cc_filter': ([c_void_p, c_i64, c_void_p, c_void_p, C.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     'vg_hist256': ([c_void_p, c_i64, c_void_p, c_void_p, c_void_p], c_int),
     'vg_threshold_mask': ([c_void_p, c_i64, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_edt_scratch_bytes': ([c_int, c_int, c_int, c_int], c_i64),
+    'vg_edt': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p], c_int),
+    'vg_fill_holes_mark': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
+    'vg_fill_holes_apply': ([c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p], c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

@@ -3,13 +3,16 @@ reference's GanMonitor.stitch_subvolumes writes a TIFF (custom_callback.py:202-2
 device: a threshold (a number, or Otsu's from the 256-bin histogram of pred.astype('uint8')), 3-D connected components numbered as
 scipy.ndimage.label numbers them, and the removal of components below a voxel count (skimage.morphology.remove_small_objects).  The
 arithmetic runs in csrc/vg_components.hip (include/vangan_hip.h "Prediction post-processing"); this module owns
-buffers and checks.
+buffers and checks.  Then what measures that network, at the end of the file: the exact Euclidean distance transform
+(scipy.ndimage.distance_transform_edt), hole filling (scipy.ndimage.binary_fill_holes) and the vessel radius, the two chained
+(csrc/vg_edt.hip).
 
 A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost, a contiguous torch tensor ON THE DEVICE: a prediction is fp32, a mask uint8 or bool
 (0 is background).  Arguments are checked before the device is touched (ValueError).  Every function only enqueues unless a read-back
 is asked for (return_threshold, return_sizes, return_info); a read-back raises RuntimeError on a non-zero status word of vg_cc_label."""
 from __future__ import annotations
 
+import ctypes
 import math
 import numbers
 import operator
@@ -34,7 +37,12 @@ def label_tiles(shape) -> int:
     return math.prod(-(-s // t) for s, t in zip(shape, TILE))
 
 
-def _device_volume(x, dtypes, what: str, labelled: bool = False) -> Tuple[torch.Tensor, Tuple[int, int, int]]:
+def _on_device(x, what: str):
+    if not x.is_cuda:
+        raise ValueError('%s must be on the device, got a tensor on %s' % (what, x.device))
+
+
+def _device_volume(x, dtypes, what: str, labelled: bool = False, check_device: bool = True) -> Tuple[torch.Tensor, Tuple[int, int, int]]:
     """x and its (X, Y, Z); everything a wrong argument can be is rejected here, on the host -- type, shape, dtype, layout and size first,
     none of which needs a device, then where the tensor lives.  labelled: the volume goes through vg_cc_label, which has a tile limit."""
     if not isinstance(x, torch.Tensor):
@@ -49,8 +57,8 @@ def _device_volume(x, dtypes, what: str, labelled: bool = False) -> Tuple[torch.
     if labelled and label_tiles(shape) > MAX_TILES:
         raise ValueError('%s of shape %s is %d tiles of %dx%dx%d voxels; the labelling serves at most %d (a very thin volume: reshape it)'
                          % ((what, shape, label_tiles(shape)) + TILE + (MAX_TILES,)))
-    if not x.is_cuda:
-        raise ValueError('%s must be on the device, got a tensor on %s' % (what, x.device))
+    if check_device:
+        _on_device(x, what)
     return x.detach(), shape
 
 
@@ -222,10 +230,11 @@ def remove_small_objects(mask, min_size=64, connectivity=1, return_labels: bool 
     return (out, renum, counts[1:2]) if return_labels else out
 
 
-def vessel_mask(pred, threshold=127.5, min_size=64, connectivity=3, return_info: bool = False):
+def vessel_mask(pred, threshold=127.5, min_size=64, connectivity=3, return_info: bool = False, fill_holes: bool = False):
     """binarise_prediction, label_components and remove_small_objects chained: the uint8 mask [X,Y,Z] of the vascular network in the
     prediction.  Enqueue-only; return_info=True: (mask, dict(threshold, components, kept, voxels, kept_voxels)) -- the threshold used, the
-    components and the voxels above it, what is left of both -- read back in one synchronising step (RuntimeError on a non-zero status)."""
+    components and the voxels above it, what is left of both -- read back in one synchronising step (RuntimeError on a non-zero status).
+    fill_holes=True: the cavities of the kept components are closed afterwards (fill_holes below); the info counts what was there before."""
     kind, value = _threshold(threshold)
     c = _connectivity(connectivity)
     msz = _min_size(min_size)
@@ -234,12 +243,99 @@ def vessel_mask(pred, threshold=127.5, min_size=64, connectivity=3, return_info:
     with torch.cuda.device(dev):
         mask, t = _binarise(x, shape, kind, value, torch.zeros(1, dtype=torch.int32, device=dev))
         if msz <= 1 and not return_info:
-            return mask
+            return _fill(mask, shape) if fill_holes else mask
         labels, sizes, result = _label(mask, shape, c)
         out, counts, _ = _filter(labels, sizes, result, msz)
+        if fill_holes:
+            out = _fill(out, shape)
         if not return_info:
             return out
         host = _read_result(result)
         kept = [int(w) for w in counts.cpu()]
         info = dict(threshold=_t_host(t), components=host[R_K], kept=kept[1], voxels=host[R_FOREGROUND], kept_voxels=kept[0])
     return out, info
+
+
+# ------------------------------------------------------------------------------------------------ measuring the mask (csrc/vg_edt.hip)
+EDT_SQUARED_I32, EDT_DIST_F32 = 0, 1       # VG_EDT_SQUARED_I32, VG_EDT_DIST_F32
+EDT_INF = 2 ** 31 - 1                      # the squared distance where the volume has no background voxel
+
+
+def _sampling(sampling):
+    """None, or the three voxel spacings (X, Y, Z) as floats; a single number stands for all three, as in scipy."""
+    if sampling is None:
+        return None
+    if isinstance(sampling, numbers.Real) and not isinstance(sampling, bool):
+        sampling = (sampling,) * 3
+    try:
+        s = tuple(float(v) for v in sampling)
+    except (TypeError, ValueError):
+        raise ValueError('sampling is None, a number or three numbers (the voxel spacing along X, Y, Z), got %r' % (sampling,)) from None
+    if len(s) != 3 or not all(math.isfinite(v) and v > 0.0 for v in s):
+        raise ValueError('sampling is None, a number or three numbers, each finite and > 0, got %r' % (sampling,))
+    return s
+
+
+def _edt_volume(mask, labelled: bool = False):
+    """A mask whose distances are going to be taken: every squared distance in voxel units must be an int32."""
+    m, shape = _device_volume(mask, (torch.uint8, torch.bool), 'mask', labelled=labelled, check_device=False)
+    if sum(d * d for d in shape) >= 2 ** 31:
+        raise ValueError('mask of shape %s: the distance transform serves X^2 + Y^2 + Z^2 < 2^31' % (shape,))
+    _on_device(m, 'mask')
+    return (m.view(torch.uint8) if m.dtype == torch.bool else m), shape
+
+
+def _edt(m: torch.Tensor, shape, s, squared: bool) -> torch.Tensor:
+    dev = m.device
+    out = torch.empty(shape, dtype=torch.int32 if squared else torch.float32, device=dev)
+    scratch, nbytes = _scratch('vg_edt_scratch_bytes', shape[0], shape[1], shape[2], 0 if s is None else 1, dev=dev)
+    s3 = None if s is None else (ctypes.c_double * 3)(*s)                  # host memory, read before the call returns
+    _check(lib.vg_edt(_p(m), shape[0], shape[1], shape[2], s3, _p(out), EDT_SQUARED_I32 if squared else EDT_DIST_F32, _p(scratch), nbytes,
+                      stream()), 'vg_edt')
+    return out
+
+
+def distance_transform_edt(mask, sampling=None, squared: bool = False):
+    """scipy.ndimage.distance_transform_edt(mask, sampling) on the device: fp32 [X,Y,Z], the exact Euclidean distance of every foreground
+    voxel to the nearest background voxel (0 on the background) -- the fp32 rounding of the fp64 square root of the exact squared
+    distance.  sampling: None (voxel units; integer arithmetic), a number or three numbers, the voxel spacing along X, Y, Z (fp64
+    arithmetic).  squared=True (sampling=None only): the int32 squared distances.  A volume WITHOUT any background voxel gives +inf
+    everywhere (2^31 - 1 squared), where scipy returns numbers without meaning.  Needs X^2 + Y^2 + Z^2 < 2^31.  Enqueue-only; temporary
+    device memory: 8 bytes per voxel, 16 with a sampling."""
+    s = _sampling(sampling)
+    if squared and s is not None:
+        raise ValueError('squared=True returns the integer squared distances in voxel units: it takes no sampling')
+    m, shape = _edt_volume(mask)
+    with torch.cuda.device(m.device):
+        return _edt(m, shape, s, bool(squared))
+
+
+def _fill(m: torch.Tensor, shape) -> torch.Tensor:
+    """The uint8 device mask m with its holes closed: the background components (connectivity 1) that reach no face become foreground."""
+    dev, n = m.device, m.numel()
+    labels, _, _ = _label((m == 0).view(torch.uint8), shape, 1)
+    flags = torch.empty(sizes_capacity(n), dtype=torch.uint8, device=dev)
+    out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    _check(lib.vg_fill_holes_mark(_p(labels), shape[0], shape[1], shape[2], _p(flags), stream()), 'vg_fill_holes_mark')
+    _check(lib.vg_fill_holes_apply(_p(m), _p(labels), _p(flags), n, _p(out), stream()), 'vg_fill_holes_apply')
+    return out
+
+
+def fill_holes(mask):
+    """scipy.ndimage.binary_fill_holes(mask) with its default structure, on the device: uint8 [X,Y,Z] (0 / 1), the mask with every
+    background component that does not reach the border of the volume through face neighbours turned into foreground.  Enqueue-only;
+    temporary device memory as label_components."""
+    m, shape = _mask_volume(mask)
+    with torch.cuda.device(m.device):
+        return _fill(m, shape)
+
+
+def vessel_radius(mask, sampling=None, fill: bool = True):
+    """distance_transform_edt(fill_holes(mask) if fill else mask, sampling): the radius map of a vessel mask, fp32 [X,Y,Z].  fill=True
+    closes hollow lumina first, so that a vessel is measured to its wall and not to its cavity.  Enqueue-only."""
+    s = _sampling(sampling)
+    if not fill:
+        return distance_transform_edt(mask, s)
+    m, shape = _edt_volume(mask, labelled=True)
+    with torch.cuda.device(m.device):
+        return _edt(_fill(m, shape), shape, s, False)
