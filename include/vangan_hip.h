@@ -788,9 +788,42 @@ int vg_outlier_limits(const void* vol, int dtype, int64_t n, const float* mean_s
  *   the INVERTED mask (1 where mask is 0) at connectivity 1.  mark: zeroes flags -- n / 2 + 2 BYTES, one per possible label -- and
  *   sets flags[l] = 1 for every label l >= 1 met on one of the six faces of the volume (plain stores of one value).  apply:
  *   out[v] = mask[v] != 0 || !flags[labels[v]] (0 / 1); a label outside [1, n / 2 + 2) is never used as an index.  out and mask must not overlap; 16-byte loads where labels, mask and out allow.
+ *
+ * The centreline (csrc/vg_skeleton.hip; skeletonize, skeleton_nodes, vessel_centreline): exact topological
+ * thinning of the mask to a curve skeleton, one voxel wide, with the topology of the mask.  THE ALGORITHM.  Foreground is mask != 0 and
+ * is 26-connected; everything outside the volume is background, which is 6-connected.  The neighbourhood of a voxel p is its 27-bit
+ * code: bit 9 (dx + 1) + 3 (dy + 1) + (dz + 1) is the foreground state of p + (dx, dy, dz), bit 13 (p itself) taken as 0.  p is SIMPLE
+ * when T26(p) = 1 and T6bar(p) = 1 (Malandain-Bertrand): T26 = the number of 26-connected components of the foreground among the 26
+ * neighbours; T6bar = the number of 6-connected components of the background within the 18-neighbourhood (the 26 neighbours minus the 8
+ * corners) that contain at least one of the six face neighbours.  p is an END POINT when fewer than two of its 26 neighbours are
+ * foreground.  Directions d = 0 .. 5: (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1).  Subfields s = 0 .. 7:
+ * s = 4 (x & 1) + 2 (y & 1) + (z & 1).  A PASS runs for d = 0 .. 5: (1) mark: C_d = the foreground voxels whose neighbour at p + d is
+ * background, in the image as it is now; (2) for s = 0 .. 7 in order, delete simultaneously every p in C_d of subfield s that, in the
+ * image as it is at the start of this sub-step, is still foreground, is not an end point and is simple.  Passes repeat until one
+ * deletes nothing.  Two voxels of one subfield differ by an even amount on every axis, so neither lies in the other's 3x3x3 window,
+ * which is all the two tests read: deleting a sub-step's voxels at once equals deleting them one by one in any order, every deletion
+ * is of a simple point (the topology is kept), and the result is a function of the mask and this schedule alone -- bit-identical on
+ * every run and equal to the numpy restatement (tests/skeleton_restate.py).
+ * vg_skeleton_begin: packs the mask into the scratch as bits -- word w (uint64) of row (x, y) holds z = 64 w .. 64 w + 63, bit z & 63,
+ *   ceil(Z / 64) words per row, padding bits 0.  One launch.  scratch: vg_skeleton_scratch_bytes(X, Y, Z, n_passes) bytes, 16-byte
+ *   aligned: two bit volumes of al16(8 X Y ceil(Z / 64)) bytes each (the image, the marks of a direction), then al16(4 n_passes) bytes
+ *   that the entries never touch by themselves -- room for deleted_out.  begin and end need the size for n_passes = 1.
+ * vg_skeleton_passes: n_passes (1 .. VG_SKELETON_MAX_PASSES) passes on the packed image, in place; may be called again to go on
+ *   thinning without repacking.  deleted_out: n_passes uint32 words ON THE DEVICE, 4-byte aligned, anywhere -- the tail of the scratch
+ *   (offset 2 al16(8 X Y ceil(Z / 64))) or a buffer of the caller's beside it, not inside the two bit volumes; zeroed by the entry,
+ *   then deleted_out[i] = voxels deleted by pass i.  A pass is 6 x (1 + 8) launches (fewer where X or Y is 1: a subfield without rows
+ *   is not launched); every launch of pass i > 0 first reads deleted_out[i - 1] and leaves at once when it is 0, so the passes after
+ *   convergence cost their launches only and leave deleted_out[i] = 0.  Pass 0 of a call always runs.  One integer atomic per wave
+ *   (the count); the image is updated by plain stores of words that one thread owns.
+ * vg_skeleton_end: unpacks the image to out (uint8[n], 0 / 1; 16-byte stores where out is 16-byte aligned).  One launch; the scratch
+ *   is only read, so thinning may go on afterwards.
+ * vg_neighbour_count26: out[v] (uint8) = the number of foreground voxels among the 26 neighbours of v where mask[v] != 0 (saturated at
+ *   255, which 26 never reaches), 0 on the background.  On a skeleton: 1 = end point, 2 = segment, >= 3 = junction, 0 = isolated
+ *   voxel.  One launch, no scratch; out and mask must not overlap.
  * --------------------------------------------------------------------------------------------- */
 #define VG_EDT_SQUARED_I32 0
 #define VG_EDT_DIST_F32 1
+#define VG_SKELETON_MAX_PASSES 4096
 #define VG_CC_TILE_X 8
 #define VG_CC_TILE_Y 8
 #define VG_CC_TILE_Z 64
@@ -807,6 +840,11 @@ int vg_edt(const uint8_t* mask, int X, int Y, int Z, const double* sampling3_or_
            int64_t scratch_bytes, vg_stream_t stream);
 int vg_fill_holes_mark(const int32_t* labels, int X, int Y, int Z, uint8_t* flags, vg_stream_t stream);
 int vg_fill_holes_apply(const uint8_t* mask, const int32_t* labels, const uint8_t* flags, int64_t n, uint8_t* out, vg_stream_t stream);
+int64_t vg_skeleton_scratch_bytes(int X, int Y, int Z, int n_passes);
+int vg_skeleton_begin(const uint8_t* mask, int X, int Y, int Z, void* scratch, int64_t scratch_bytes, vg_stream_t stream);
+int vg_skeleton_passes(int X, int Y, int Z, int n_passes, void* scratch, int64_t scratch_bytes, uint32_t* deleted_out, vg_stream_t stream);
+int vg_skeleton_end(int X, int Y, int Z, const void* scratch, int64_t scratch_bytes, uint8_t* out, vg_stream_t stream);
+int vg_neighbour_count26(const uint8_t* mask, int X, int Y, int Z, uint8_t* out, vg_stream_t stream);
 
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */

@@ -157,6 +157,11 @@ _SIGS = {
     'vg_edt': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p], c_int),
     'vg_fill_holes_mark': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
     'vg_fill_holes_apply': ([c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p], c_int),
+    'vg_skeleton_scratch_bytes': ([c_int, c_int, c_int, c_int], c_i64),
+    'vg_skeleton_begin': ([c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p], c_int),
+    'vg_skeleton_passes': ([c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p], c_int),
+    'vg_skeleton_end': ([c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p], c_int),
+    'vg_neighbour_count26': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

@@ -5,11 +5,14 @@ scipy.ndimage.label numbers them, and the removal of components below a voxel co
 arithmetic runs in csrc/vg_components.hip (include/vangan_hip.h "Prediction post-processing"); this module owns
 buffers and checks.  Then what measures that network, at the end of the file: the exact Euclidean distance transform
 (scipy.ndimage.distance_transform_edt), hole filling (scipy.ndimage.binary_fill_holes) and the vessel radius, the two chained
-(csrc/vg_edt.hip).
+(csrc/vg_edt.hip).  Then its centreline: exact topological thinning to a one-voxel-wide curve skeleton, the
+degree of every skeleton voxel, and the radius along the centreline (csrc/vg_skeleton.hip).
 
 A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost, a contiguous torch tensor ON THE DEVICE: a prediction is fp32, a mask uint8 or bool
 (0 is background).  Arguments are checked before the device is touched (ValueError).  Every function only enqueues unless a read-back
-is asked for (return_threshold, return_sizes, return_info); a read-back raises RuntimeError on a non-zero status word of vg_cc_label."""
+is asked for (return_threshold, return_sizes, return_info); a read-back raises RuntimeError on a non-zero status word of vg_cc_label.
+The one exception is thinning until nothing changes (skeletonize with max_passes=None and what builds on it), which reads the voxels
+deleted by every four passes back to know when to stop; skeletonize(mask, max_passes=k) only enqueues."""
 from __future__ import annotations
 
 import ctypes
@@ -230,11 +233,19 @@ def remove_small_objects(mask, min_size=64, connectivity=1, return_labels: bool 
     return (out, renum, counts[1:2]) if return_labels else out
 
 
-def vessel_mask(pred, threshold=127.5, min_size=64, connectivity=3, return_info: bool = False, fill_holes: bool = False):
+def vessel_mask(pred, threshold=127.5, min_size=64, connectivity=3, return_info: bool = False, fill_holes: bool = False, skeleton: bool = False):
     """binarise_prediction, label_components and remove_small_objects chained: the uint8 mask [X,Y,Z] of the vascular network in the
     prediction.  Enqueue-only; return_info=True: (mask, dict(threshold, components, kept, voxels, kept_voxels)) -- the threshold used, the
     components and the voxels above it, what is left of both -- read back in one synchronising step (RuntimeError on a non-zero status).
-    fill_holes=True: the cavities of the kept components are closed afterwards (fill_holes below); the info counts what was there before."""
+    fill_holes=True: the cavities of the kept components are closed afterwards (fill_holes below); the info counts what was there before.
+    skeleton=True: skeletonize (below) of the mask that is returned comes as one more value at the end -- (mask, skeleton) or
+    (mask, info, skeleton); it thins until nothing changes, which reads a few words back after every four passes."""
+    if skeleton:
+        got = vessel_mask(pred, threshold, min_size, connectivity, return_info, fill_holes)
+        mask = got[0] if return_info else got
+        with torch.cuda.device(mask.device):
+            skel = _thin(mask, tuple(mask.shape), None)[0]
+        return (got[0], got[1], skel) if return_info else (mask, skel)
     kind, value = _threshold(threshold)
     c = _connectivity(connectivity)
     msz = _min_size(min_size)
@@ -339,3 +350,101 @@ def vessel_radius(mask, sampling=None, fill: bool = True):
     m, shape = _edt_volume(mask, labelled=True)
     with torch.cuda.device(m.device):
         return _edt(_fill(m, shape), shape, s, False)
+
+
+# ------------------------------------------------------------------------------------------------ the centreline (csrc/vg_skeleton.hip)
+SKELETON_CHUNK = 4                         # passes enqueued between two read-backs when thinning until nothing changes
+SKELETON_MAX_PASSES = 4096                 # VG_SKELETON_MAX_PASSES: the passes of one call of vg_skeleton_passes
+
+
+def _max_passes(max_passes):
+    if max_passes is None:
+        return None
+    try:
+        k = operator.index(max_passes)
+    except TypeError:
+        raise ValueError('max_passes is None or an integer >= 1, got %r' % (max_passes,)) from None
+    if isinstance(max_passes, bool) or k < 1:
+        raise ValueError('max_passes is None or an integer >= 1, got %r' % (max_passes,))
+    return k
+
+
+def _skeleton_volume(mask):
+    m, shape = _device_volume(mask, (torch.uint8, torch.bool), 'mask')
+    return (m.view(torch.uint8) if m.dtype == torch.bool else m), shape
+
+
+def _thin(m: torch.Tensor, shape, max_passes, read: bool = False):
+    """(skeleton, deleted): the uint8 device mask m thinned.  max_passes None: chunks of SKELETON_CHUNK passes, the counts of each read
+    back, until a pass deleted nothing; deleted is the list of counts up to that 0.  An int: exactly that many passes, nothing read
+    back unless read, deleted then the list of their counts, else None."""
+    dev = m.device
+    X, Y, Z = shape
+    chunk = SKELETON_CHUNK if max_passes is None else min(max_passes, SKELETON_MAX_PASSES)
+    scratch, nbytes = _scratch('vg_skeleton_scratch_bytes', X, Y, Z, chunk, dev=dev)
+    counts = scratch[nbytes - (4 * chunk + 15) // 16 * 16:][:4 * chunk].view(torch.int32)      # the tail the query leaves for them
+    _check(lib.vg_skeleton_begin(_p(m), X, Y, Z, _p(scratch), nbytes, stream()), 'vg_skeleton_begin')
+    deleted, left = [], max_passes
+    while True:
+        k = chunk if left is None else min(left, chunk)
+        _check(lib.vg_skeleton_passes(X, Y, Z, k, _p(scratch), nbytes, _p(counts), stream()), 'vg_skeleton_passes')
+        if left is None or read:
+            deleted += [int(c) for c in counts[:k].cpu()]
+        if left is None:
+            if 0 in deleted:
+                deleted = deleted[:deleted.index(0) + 1]
+                break
+        else:
+            left -= k
+            if left == 0:
+                break
+    out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    _check(lib.vg_skeleton_end(X, Y, Z, _p(scratch), nbytes, _p(out), stream()), 'vg_skeleton_end')
+    return out, (deleted if max_passes is None or read else None)
+
+
+def skeletonize(mask, max_passes=None, return_info: bool = False):
+    """The curve skeleton of mask on the device: uint8 [X,Y,Z] (0 / 1), a subset of the mask, one voxel wide, with the mask's topology
+    -- the same 26-components of the foreground, 6-components of the background, tunnels and cavities -- and the end points of its
+    branches kept.  Exact topological thinning by directional sub-iterations over eight parity subfields (include/vangan_hip.h has the
+    algorithm): the result depends on the mask alone, bit for bit.  Foreground is 26-connected, the outside of the volume
+    is background.  max_passes=None: thin until a pass deletes nothing -- passes are enqueued four at a time and their counts read back
+    (a synchronising copy per chunk; a vessel of radius r needs about r + 1 passes, a solid block of side L about L / 2).  max_passes=k:
+    exactly k passes, enqueue-only; the passes after one that deleted nothing do nothing.  return_info=True: (skeleton,
+    dict(passes, deleted, converged)) -- the passes run, the voxels each deleted, and whether one of them deleted nothing; with
+    max_passes=k this reads the k counts back.  A cavity stays enclosed by a closed surface of skeleton: fill_holes first where a
+    hollow lumen is meant to be a vessel (vessel_centreline does).  Temporary device memory: a quarter of a byte per voxel."""
+    k = _max_passes(max_passes)
+    m, shape = _skeleton_volume(mask)
+    with torch.cuda.device(m.device):
+        out, deleted = _thin(m, shape, k, bool(return_info))
+    if not return_info:
+        return out
+    return out, dict(passes=len(deleted), deleted=deleted, converged=0 in deleted)
+
+
+def skeleton_nodes(skel):
+    """uint8 [X,Y,Z]: for every foreground voxel of skel (a skeleton, or any mask) the number of its 26 neighbours that are
+    foreground, 0 on the background.  On a skeleton 1 is an end point, 2 a voxel of a segment, 3 or more a junction (0: a voxel on its
+    own).  Enqueue-only."""
+    m, shape = _skeleton_volume(skel)
+    with torch.cuda.device(m.device):
+        out = torch.empty(shape, dtype=torch.uint8, device=m.device)
+        _check(lib.vg_neighbour_count26(_p(m), shape[0], shape[1], shape[2], _p(out), stream()), 'vg_neighbour_count26')
+    return out
+
+
+def vessel_centreline(mask, sampling=None, fill: bool = True):
+    """(skeleton, radius): skeletonize of the mask and vessel_radius(mask, sampling, fill) multiplied by it -- the radius of the vessel
+    at every voxel of its centreline, 0 elsewhere (also where the radius is +inf: a volume without background); uint8 and fp32
+    [X,Y,Z].  fill=True: both are taken of fill_holes(mask), so that a
+    hollow lumen is measured to its wall and does not leave a shell of centreline around its cavity.  The thinning reads its counts
+    back every four passes."""
+    s = _sampling(sampling)
+    m, shape = _edt_volume(mask, labelled=bool(fill))
+    with torch.cuda.device(m.device):
+        if fill:
+            m = _fill(m, shape)
+        skel = _thin(m, shape, None)[0]
+        radius = _edt(m, shape, s, False)
+        return skel, torch.where(skel != 0, radius, torch.zeros((), dtype=radius.dtype, device=radius.device))

@@ -986,15 +986,18 @@ class VanGan:
         return self.stitch_subvolumes(gen, img, subvol_size, **stitch_kw)
 
     def segment_mask(self, gen: str, raw, subvol_size=None, *, threshold=127.5, min_size=64, connectivity=3, return_info: bool = False,
-                     fill_holes: bool = False, **kw):
+                     fill_holes: bool = False, skeleton: bool = False, **kw):
         """Raw volume -> binary vascular network on the device: segment_volume(gen, raw, subvol_size, **kw) followed by vessel_mask
         (van_gan_amd/postprocess.py) -- threshold (a number, a device word or 'otsu'), 3-D connected components, removal of the
         components below min_size voxels, and with fill_holes=True the closing of their cavities; uint8 [X,Y,Z].  return_info=True:
-        (mask, dict(threshold, components, kept, voxels, kept_voxels)).  The three post-processing arguments are checked before
+        (mask, dict(threshold, components, kept, voxels, kept_voxels)).  skeleton=True: the curve skeleton of the returned mask
+        (postprocess.skeletonize) comes as one more value at the end.  The three post-processing arguments are checked before
         anything runs."""
         from . import postprocess
         postprocess._threshold(threshold), postprocess._min_size(min_size), postprocess._connectivity(connectivity)
         pred = self.segment_volume(gen, raw, subvol_size, **kw)
+        if skeleton:
+            return postprocess.vessel_mask(pred, threshold, min_size, connectivity, return_info, fill_holes=fill_holes, skeleton=True)
         return postprocess.vessel_mask(pred, threshold, min_size, connectivity, return_info, fill_holes=fill_holes)
 
     # ------------------------------------------------------------------------------------------------
