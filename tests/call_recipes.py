@@ -11,7 +11,8 @@ The decoder blocks' fused backward launches (vg_shortcut_dgrad_concat_norm / vg_
 (ops.ConvLayer.dgrad_concat_norm / dgrad_concat): decoder_blocks() lists them explicitly per config.
 
 cases_of() is the one loop that turns walks into cases: call_cases() feeds it the three BASELINE walks, ragged_call_cases() the walks
-of layer_recipes.RAGGED_CONFIGS / RAGGED_INFER_CONFIGS (tests/test_gpu_ragged.py, tests/test_ragged_coverage.py).
+of layer_recipes.RAGGED_CONFIGS / RAGGED_INFER_CONFIGS (tests/test_gpu_ragged.py, tests/test_ragged_coverage.py), batch3_call_cases()
+the walks of layer_recipes.BATCH3_CONFIGS (tests/test_gpu_batch3.py, tests/test_batch3_coverage.py).
 
 Helper module (no tests in here)."""
 from __future__ import annotations
@@ -160,6 +161,37 @@ def ragged_call_cases() -> Dict[str, dict]:
     have = {c for case in call_cases().values() for c in case['covers']}
     cases = cases_of(LR.all_ragged_walks(), LR.RAGGED_CONFIGS)
     return {cid: c for cid, c in cases.items() if c['kind'] == 'fin' or not all(cv in have for cv in c['covers'])}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# batch 3 (layer_recipes.BATCH3_CONFIGS)
+# ----------------------------------------------------------------------------------------------------------------------
+def batch3_needed_calls():
+    """Every (entry point, regime) the batch-3 walks record."""
+    return sorted({c for _, calls in LR.all_batch3_walks().values() for c in calls}, key=repr)
+
+
+def batch3_needed_fin():
+    """Every (forward variant, tail job shape) the batch-3 walks record."""
+    return sorted({(v, fin_shape(r)) for recs, _ in LR.all_batch3_walks().values() for k, _, v, r in recs if k == 'fwd' and r.get('fin')})
+
+
+@functools.lru_cache(maxsize=None)
+def batch3_call_cases() -> Dict[str, dict]:
+    """cases_of the batch-3 walks, filtered as ragged_call_cases() is: a non-convolution case is dropped only if call_cases() or
+    ragged_call_cases() covers every (entry point, regime) it covers, field for field (regimes carry N: none is); a tail case never (its
+    key has no N in it, and the recorded call -- three samples' statistics, the kernel's tile walk over 3 samples -- is a batch-3 one).
+    A tail whose recorded call costs more than layer_recipes.macs_cap() is shrunk like its convolution's representative."""
+    have = {c for cases in (call_cases(), ragged_call_cases()) for case in cases.values() for c in case['covers']}
+    cases = cases_of(LR.all_batch3_walks(), LR.BATCH3_CONFIGS)
+    cases = {cid: c for cid, c in cases.items() if c['kind'] == 'fin' or not all(cv in have for cv in c['covers'])}
+    cap = LR.macs_cap()
+    for c in cases.values():
+        if c['kind'] == 'fin' and c['macs'] > cap:
+            r = LR.shrink_call(c['recipe'], c['variant'], cap)
+            if r is not c['recipe']:
+                c.update(recipe=r, macs=LR.recipe_macs(r), shrunk=True, recorded=c['recipe'])
+    return cases
 
 
 def fin_stress_cases() -> Dict[str, dict]:

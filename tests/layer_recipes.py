@@ -8,7 +8,8 @@ becomes its representative; tests/test_gpu_layers.py replays the representative 
 compares it with the oracle's convolution (autograd for the two gradients), tests/test_variant_coverage.py (CPU) proves the
 representatives cover every variant of BASELINE configs 2, 3 and 4.  The same for the sliding-window inference forward
 (INFER_CONFIGS; tests/test_gpu_infer_layers.py) and for patches whose level grids are no powers of two (RAGGED_CONFIGS /
-RAGGED_INFER_CONFIGS; tests/test_gpu_ragged.py, tests/test_ragged_coverage.py).
+RAGGED_INFER_CONFIGS; tests/test_gpu_ragged.py, tests/test_ragged_coverage.py), and for the train steps at the reference's own
+per-GPU batch of three (BATCH3_CONFIGS; tests/test_gpu_batch3.py, tests/test_batch3_coverage.py).
 
 Helper module (no tests in here)."""
 from __future__ import annotations
@@ -288,6 +289,91 @@ def ragged_only_variants():
     return sorted(kv for kv in ragged_representatives() if kv not in have)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# batch 3: the reference's own per-GPU training batch
+# ----------------------------------------------------------------------------------------------------------------------
+# The generator's kernels run at N = 3 and 6, the discriminator's at N = 6 and 9 (backward_both's 3B launch); every other walk of this
+# module has a batch of 1 or 2.  The four power-of-two patches of CONFIGS and the smallest ragged one; the sliding-window inference does
+# not depend on the training batch: no inference walks.  Nothing above this line depends on these.  (walk_config's dry-run arena is an
+# untouched torch.empty of B * S * 10400 bytes: 65 GB of address space at 128^3 B3, none of it ever written.)
+BATCH3_CONFIGS = {
+    '32^3 B3': ((32, 32, 32), 3),
+    '64^3 B3': ((64, 64, 64), 3),
+    '128x128x64 B3': ((128, 128, 64), 3),
+    '128^3 B3': ((128, 128, 128), 3),
+    '32x48x80 B3': ((32, 48, 80), 3),
+}
+BATCH3_N = (3, 6, 9)
+
+
+@functools.lru_cache(maxsize=None)
+def all_batch3_walks():
+    """config -> (conv records, non-convolution calls): the train walks of BATCH3_CONFIGS."""
+    return {name: walk_config(dims, B) for name, (dims, B) in BATCH3_CONFIGS.items()}
+
+
+def recipe_n(recipe) -> int:
+    return recipe['src']['N'] if 'src' in recipe else recipe['N']
+
+
+def macs_cap() -> float:
+    """No case of a later module is heavier than the heaviest one of tests/test_gpu_layers.py (down2's data gradient at 128^3 B1)."""
+    return max(r['macs'] for r in representatives().values())
+
+
+def shrink_call(recipe, variant, cap):
+    """shrink_recipe for all three kinds and for a batch that has to stay what it is: a cheaper call of the same layer with the SAME
+    number of samples for which the CPU dry run of the rebuilt call (replay_variant) still reports `variant` -- one axis halved at a
+    time, greedily, until the call costs no more than `cap` MACs.  Returns `recipe` itself if no such call exists."""
+    def with_dims(r, dims):
+        out = dict(r, layer=dict(r['layer'], in_dims=tuple(dims)))
+        if 'src' in r:
+            out['src'] = dict(r['src'], dims=tuple(dims))
+        if r.get('fin'):
+            out['fin'] = dict(r['fin'], count=float(math.prod(out_grid(out))))
+        return out
+
+    best, moved = recipe, True
+    while moved and recipe_macs(best) > cap:
+        moved = False
+        dims = tuple(best['layer']['in_dims'])
+        for a in sorted(range(3), key=lambda a: -dims[a]):
+            if dims[a] % 4 or dims[a] < 16:
+                continue
+            cand = with_dims(best, dims[:a] + (dims[a] // 2,) + dims[a + 1:])
+            try:
+                same = replay_variant(cand) == variant
+            except Exception:                       # no tile plan for the shrunk grid: not a candidate
+                same = False
+            if same:
+                best, moved = cand, True
+                break
+    return best if recipe_macs(best) <= cap else recipe
+
+
+@functools.lru_cache(maxsize=None)
+def batch3_representatives() -> Dict[Tuple[str, str], dict]:
+    """(kind, variant) -> {'recipe', 'config', 'layer', 'macs'} for every variant of the batch-3 walks: the cheapest call OF A BATCH-3 WALK
+    that selects it, replayed as recorded -- N = 3, 6 or 9 -- unless it costs more than macs_cap(): then with axes halved while the dry
+    run keeps the identical variant string (shrink_call; 'shrunk': True, 'recorded': the walk's own recipe).  The batch is never
+    touched."""
+    best = _cheapest(all_batch3_walks())
+    cap = macs_cap()
+    for key, b in best.items():
+        if b['macs'] > cap:
+            r = shrink_call(b['recipe'], key[1], cap)
+            if r is not b['recipe']:
+                b.update(recipe=r, macs=recipe_macs(r), shrunk=True, recorded=b['recipe'])
+    return best
+
+
+def batch3_only_variants():
+    """The (kind, variant) pairs of the batch-3 walks that no older table has a case for: representatives(),
+    inference_representatives(), ragged_representatives()."""
+    have = set(representatives()) | set(inference_representatives()) | set(ragged_representatives())
+    return sorted(kv for kv in batch3_representatives() if kv not in have)
+
+
 def replay_variant(recipe) -> str:
     """recipe_variant for all three kinds: the variant the call that run_recipe rebuilds from `recipe` selects, by a CPU dry run on empty
     tensors (a data gradient may be issued in several launches of one variant: the set must have one element)."""
@@ -409,8 +495,16 @@ def ref_operand(sr, host, pad, dt, storage=torch.bfloat16):
     return bf(a, storage)
 
 
+def _f64_pair(got, ref):
+    """Both in float64 on one device: where they already share one (a device-side reference of 600 M elements at 128^3, batch 3) the
+    comparison stays there -- the same float64 arithmetic without two 5 GB copies to the host -- otherwise on the host."""
+    if got.device == ref.device:
+        return got.double(), ref.double()
+    return got.double().cpu(), ref.double().cpu()
+
+
 def close_bf16(got, ref, name='', rel=1.2e-2, floor=2e-3):
-    got, ref = got.double().cpu(), ref.double().cpu()
+    got, ref = _f64_pair(got, ref)
     tol = rel * ref.abs() + floor * ref.abs().max() + 1e-30
     bad = (got - ref).abs() > tol
     assert not bad.any(), '%s: %d/%d outside tolerance, max err %.3e (max ref %.3e)' % (
@@ -418,7 +512,7 @@ def close_bf16(got, ref, name='', rel=1.2e-2, floor=2e-3):
 
 
 def rel_l2(got, ref):
-    got, ref = got.double().cpu(), ref.double().cpu()
+    got, ref = _f64_pair(got, ref)
     return float((got - ref).norm() / (ref.norm() + 1e-30))
 
 

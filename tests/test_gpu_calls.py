@@ -323,7 +323,9 @@ def test_stem_shortcut_on_a_near_constant_volume(kind):
 # the loss chain at the configs' (B, dims)
 # ----------------------------------------------------------------------------------------------------------------------
 _LOSS_SHAPES = {'128^3 B1': (1, (128, 128, 128)), '64^3 B2': (2, (64, 64, 64)), '128x128x64 B2': (2, (128, 128, 64)),
-                '32^3 B1': (1, (32, 32, 32)), 'odd S B2': (2, (33, 35, 37))}
+                '32^3 B1': (1, (32, 32, 32)), 'odd S B2': (2, (33, 35, 37)),
+                # the reference's own per-GPU batch: samples 1 and 2 of an odd S start on different alignments (S and 2S are no multiples of 4)
+                '32^3 B3': (3, (32, 32, 32)), 'odd S B3': (3, (33, 35, 37))}
 
 
 def _ssim_ref(t, p):
@@ -344,7 +346,7 @@ def _ssim_ref(t, p):
 @pytest.mark.parametrize('cfg', sorted(_LOSS_SHAPES))
 def test_loss_chain_at_config_shapes(cfg):
     """min-max (two ties of the min and of the max further apart than the reduction grid, so the tie counts add across workgroups; an odd
-    S puts sample 1 on an unaligned start and its extrema in the scalar tail) -> BCE (p exactly 0 and 1 at the arg-extrema: clipped,
+    S puts samples 1 and 2 on unaligned starts and their extrema in the scalar tail) -> BCE (p exactly 0 and 1 at the arg-extrema: clipped,
     zero gradient) -> min-max backward; MSE, MSE against a constant on bf16 logits; SSIM loss and gradient (faces and edges included)."""
     from oracle import vangan_oracle as O
     from van_gan_amd import ops
@@ -355,9 +357,9 @@ def test_loss_chain_at_config_shapes(cfg):
     x = torch.tanh(torch.randn(B, S, generator=g, device=dev) * 2)
     for b in range(B):
         hi, lo = float(x[b].max()) + 0.25, float(x[b].min()) - 0.25
-        far = (S - 1, 5) if (b == 1 and S % 4) else (3, S - 700)              # sample 1 of an odd S: extrema in the scalar tail
+        far = (S - 1, 5) if (b >= 1 and S % 4) else (3, S - 700)              # samples >= 1 of an odd S: extrema in the scalar tail
         x[b, far[0]] = hi; x[b, far[1]] = hi
-        x[b, S // 2 + 1] = lo; x[b, S - 2 if b == 1 else 1] = lo
+        x[b, S // 2 + 1] = lo; x[b, S - 2 if b >= 1 else 1] = lo
     x = x.view(B, D, H, W, 1).contiguous()
     t = (torch.rand(B, D, H, W, 1, generator=g, device=dev) > 0.7).float()
     mm, y = torch.zeros(B, 4, device=dev), torch.zeros(B, D, H, W, 1, device=dev)
@@ -408,7 +410,7 @@ def test_loss_chain_at_config_shapes(cfg):
     assert err['ssim'] <= 1e-4 and err['ssim_grad'] <= 1e-3 and err['ssim_grad_faces'] <= 1e-3, err
 
 
-@pytest.mark.parametrize('cfg', ['128^3 B1', '64^3 B2', '128x128x64 B2', '32^3 B1'])
+@pytest.mark.parametrize('cfg', ['128^3 B1', '64^3 B2', '128x128x64 B2', '32^3 B1', '32^3 B3'])
 def test_skeleton_and_cldice_at_config_shapes(cfg):
     """soft skeleton (15 iterations, with and without the aux codes) -> dot_sums -> clDice coefficients and gradients, against float64
     autograd through the oracle on continuous data; and an all-zero target (empty skeleton: only the smooth terms)."""

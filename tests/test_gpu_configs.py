@@ -7,6 +7,9 @@
   config 5  256x256x128 sliding window product precision (bf16) through the stitch oracle driven by the HIP generator itself
   ragged    32x48x80, batch 1          a legal patch no tile divides: fixture train_step_32x48x80_b1.npz; 48x80x96, batch 1 (no
                                        power-of-two axis): full-size properties (layer by layer: tests/test_gpu_ragged.py)
+  batch 3   64^3, batch 3              the reference's own per-GPU batch: full-size properties; 128^3, batch 3 (its training
+                                       configuration): three product steps, finite and with a constant workspace peak (layer by
+                                       layer: tests/test_gpu_batch3.py)
 
 Full-size properties: finite losses, bf16 engine vs exact-parity (fp32 storage) engine on the same weights and inputs within
 the bf16 tolerance of tests/test_gpu_nets.py (3e-2), workspace peak constant from the second step on.
@@ -57,8 +60,8 @@ def test_train_step_matches_fixture(fixture):
         assert c > 0.9995 and rl < 5e-2, key
 
 
-@pytest.mark.parametrize('dims,B', [((128, 128, 64), 2), ((128, 128, 128), 1), ((48, 80, 96), 1)],
-                         ids=['config3 128x128x64 b2', 'config4 128^3 b1', 'ragged 48x80x96 b1'])
+@pytest.mark.parametrize('dims,B', [((128, 128, 64), 2), ((128, 128, 128), 1), ((48, 80, 96), 1), ((64, 64, 64), 3)],
+                         ids=['config3 128x128x64 b2', 'config4 128^3 b1', 'ragged 48x80x96 b1', 'batch3 64^3 b3'])
 def test_full_size_properties(dims, B):
     from van_gan_amd import VanGan
     rI, rS = O.synth_volumes(B, *dims, seed=77)
@@ -84,6 +87,30 @@ def test_full_size_properties(dims, B):
         a, b = out['bf16'][k], out['fp32'][k]
         print('   %-24s bf16 %.6f  fp32-mode %.6f' % (k, a, b))
         assert abs(a - b) <= 3e-2 * abs(b) + 1e-5, k
+
+
+def test_reference_training_configuration_128_b3():
+    """128^3 at batch 3 per GPU, the configuration the reference trains with: the bf16 product engine with noise,
+    dropout and Adam on, three steps.  All ten losses finite at every step, workspace peak constant from the second step on.  One
+    engine only (its arena is B * S * 8000 bytes + 512 MiB, about 50 GB); the kernels it selects are compared with the oracle one by one
+    in tests/test_gpu_batch3.py."""
+    from van_gan_amd import VanGan
+    dims, B = (128, 128, 128), 3
+    rI, rS = O.synth_volumes(B, *dims, seed=77)
+    rI, rS = rI.cuda(), rS.cuda()
+    eng = VanGan(dims, batch_size=B, n_devices=1, device='cuda:0', seed=3)
+    try:
+        peaks = []
+        for step in range(3):
+            r = eng.train_step(rI, rS)
+            print('   step %d  %s' % (step, '  '.join('%s %.5f' % (k, r[k]) for k in O.RESULT_KEYS)))
+            assert len(O.RESULT_KEYS) == 10 and all(math.isfinite(r[k]) for k in O.RESULT_KEYS), r
+            assert all(math.isfinite(v) for v in r.values()), r
+            peaks.append(eng.arena.peak)
+        assert peaks[1] == peaks[2], peaks
+    finally:
+        del eng
+        torch.cuda.empty_cache()
 
 
 def test_config5_sliding_window_full_size_product_precision():

@@ -98,6 +98,12 @@ def test_train_step_fp32_32_b2():
     _engine_fp32((32, 32, 32), 2)
 
 
+def test_train_step_fp32_32_b3():
+    """The reference's own per-GPU batch: the generators at N = 3 and 6, the discriminators at N = 6 and 9 (backward_both's 3B launch),
+    losses divided by the global batch 3 -- against the float64 oracle run live, with the bounds of the two tests above."""
+    _engine_fp32((32, 32, 32), 3)
+
+
 def test_stream_schedule_does_not_change_gradients():
     """The engine's schedule (two lanes + per-lane weight-gradient side streams, van_gan_amd/vangan.py) must only reorder
     independent work.  Same weights and inputs with the lanes on and off: every loss and every gradient buffer has to

@@ -22,6 +22,7 @@ CASES = {
     'smaller_than_a_tile': (1, 5, 3, 9, 3, False),
     'ragged_two_samples': (2, 11, 13, 37, 6, False),
     'ragged_two_samples_ties': (2, 11, 13, 37, 6, True),
+    'ragged_three_samples': (3, 11, 13, 37, 6, False),      # a clamp that leaves the middle sample reads a neighbour on either side
     'exactly_one_tile': (1, 8, 8, 32, 3, False),
     'interior_tiles': (1, 16, 16, 64, 15, False),
 }
@@ -151,7 +152,7 @@ def test_scan_backward_leaves_its_consumed_buffer_zero(name):
     assert torch.equal(kept + 0.25 - 0.25, r['grad_scan']), name
 
 
-@pytest.mark.parametrize('dims', [(2, 5, 3, 9), (1, 1, 1, 7), (2, 8, 8, 32)])
+@pytest.mark.parametrize('dims', [(2, 5, 3, 9), (1, 1, 1, 7), (2, 8, 8, 32), (3, 5, 3, 9)])
 def test_ssim_window_loads_stay_inside_their_sample(dims):
     """ssim_fwd_kernel / ssim_bwd_kernel request their 27-voxel windows the same way (clamped, all before the first wait).  Two samples
     adjacent in memory, volumes thinner than the window; value and gradient against the float64 oracle with the bounds of

@@ -176,6 +176,14 @@ def test_teacher_forced_train_step_32_b2():
     _check(got, grads, 'product schedule', _run.eng)
 
 
+def test_teacher_forced_train_step_32_b3():
+    """The reference's own per-GPU batch on the bf16 product schedule, noise and dropout on: the paired 6-sample generator sweep and the
+    9-sample discriminator sweep (a 6-sample and a 3-sample gradient aliased in one launch), every parameter gradient at the bounds of
+    the batch-2 test."""
+    got, grads = _run((32, 32, 32), 3, seed=1234)
+    _check(got, grads, 'product schedule B3', _run.eng)
+
+
 def test_unfused_schedule_teacher_forced_32_b2():
     """The same check for the engine with the fused launches, the paired sweeps and the LDS-DMA data gradients OFF
     (VG_FUSE_CONCAT=0 VG_FUSE_CONCAT_NORM=0 VG_BSTAT=0 VG_PAIR_BWD=0 VG_CONV_DMA=0): both schedules are held to the oracle at their OWN
