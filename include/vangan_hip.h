@@ -846,6 +846,79 @@ int vg_skeleton_passes(int X, int Y, int Z, int n_passes, void* scratch, int64_t
 int vg_skeleton_end(int X, int Y, int Z, const void* scratch, int64_t scratch_bytes, uint8_t* out, vg_stream_t stream);
 int vg_neighbour_count26(const uint8_t* mask, int X, int Y, int Z, uint8_t* out, vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The vessel graph (csrc/vg_skelgraph.hip; van_gan_amd/postprocess.py skeleton_graph, prune_spurs,
+ * network_summary, vessel_graph): the skeleton as segments and nodes with their measurements, and the removal of short terminal spurs.
+ * The same code in both storage builds.  Every entry only enqueues, allocates nothing, checks its arguments on the host before any
+ * launch (VG_EINVAL, nothing launched) and initialises its own outputs: no result depends on what a buffer held before.  Only integer
+ * atomics -- no float atomic appears anywhere in the file: equal inputs give bit-identical results on every run.
+ *
+ * THE DEFINITIONS.  Input: skel, a uint8 volume [X][Y][Z] with Z innermost, 1 <= n = X Y Z < 2^31.  Foreground is S = {skel != 0},
+ * 26-connected; outside the volume is background.  Any mask is legal, not only a skeleton.
+ * Degree and classes: deg(p) is the number of p's 26 neighbours in S (what vg_neighbour_count26 returns).  Segment voxels are
+ *   B = {p in S : deg(p) = 2}; node voxels are N = S \ B, that is deg 0, 1 or >= 3.
+ * Segments are the 26-components of B, numbered 1 .. E; nodes are the 26-components of N, numbered 1 .. V.  A cluster of adjacent
+ *   junction voxels is one node; an end voxel adjacent to a junction voxel belongs to that node.  Both are numbered as
+ *   scipy.ndimage.label(., np.ones((3,3,3))) numbers them, by raster order of the first voxel: they are vg_cc_label at connectivity 3 of
+ *   the two masks vg_skelgraph_classify writes.
+ * Segment shape: every B voxel has exactly two S-neighbours, so a segment is a simple path or a simple closed cycle.  The number of
+ *   (B voxel, N neighbour) pairs of a segment is 2 for a path and 0 for a cycle.  Two different nodes are never adjacent, so every
+ *   connection between nodes runs through a segment.
+ * Attachments: for a path, sort the two pairs (p, q) (p in the segment, q in N, 26-adjacent) by (linear index of p, linear index of q);
+ *   end 0 is the smaller pair and end 1 the larger.  seg_ends[e] = (q0, q1) as linear indices, seg_nodes[e] = (node(q0), node(q1)).  A
+ *   cycle has (-1, -1) and (0, 0).  A loop, with both ends at one node, is legal.  On the device this is a 64-bit integer atomic min
+ *   and a 64-bit integer atomic max of the key (p << 32) | q per segment.
+ * Length, exactly: the class of a step (dx, dy, dz) is c = 4 |dx| + 2 |dy| + |dz| - 1 in 0 .. 6.  seg_half_steps[e][c] (int64) sums,
+ *   over p in the segment and over every S-neighbour q of p of class c, the value 1 if q is in B and 2 if q is in N.  Every row sum is
+ *   even: 2 (voxels + 1) for a path, 2 voxels for a cycle.  With sampling = (sx, sy, sz), default 1, the step length is l_c =
+ *   sqrt((|dx| sx)^2 + (|dy| sy)^2 + (|dz| sz)^2), computed in fp64 on the host, and seg_length[e] = (sum over c = 0 .. 6 of
+ *   half[e][c] l_c) / 2 in fp64, the products and the sum evaluated left to right, each operation rounded, with no fused multiply-add.
+ * Chord and tortuosity: seg_chord[e] is the fp64 Euclidean distance between q0 and q1 under sampling -- sqrt of the left-to-right sum
+ *   of the squares of (difference of the coordinate) * spacing; 0 for a cycle or for q0 = q1.  Tortuosity is length / chord, taken in
+ *   the host's summary only.
+ * Radius (optional; an fp32 volume such as vg_edt writes): per segment, min and max over its voxels are exact (integer atomics on the
+ *   bit pattern; the values are >= 0).  The mean is deterministic, through fixed point: with D = sqrt((X sx)^2 + (Y sy)^2 + (Z sz)^2),
+ *   b = 62 - ceil(log2 n) and k = b - ceil(log2 D), both from the shape and the sampling alone, on the host, the kernel adds
+ *   llrint(r 2^k) into an int64 per segment (the product is exact: fp32 -> fp64 times a power of two) and seg_radius_mean =
+ *   sum / 2^k / voxels.  The quantisation is at most 2^-(k+1) absolute per voxel.  Voxels whose radius is negative, NaN, infinite or
+ *   above D are skipped and counted in bad2[0].
+ * Nodes: node_voxels and node_degree are int32; node_degree counts attachments, so a loop counts twice.  node_kind (uint8): 0 is
+ *   isolated, one voxel of deg 0; 1 is end, one voxel of deg 1; 2 is every other node.  node_centroid is fp64 [V + 1][3], built from
+ *   uint64 coordinate sums divided by the voxel count.
+ * Spur: a path segment with exactly one of its two nodes of kind end and seg_length < min_length.  One pruning round deletes, from S,
+ *   the voxels of every spur and the end voxel it hangs from; nothing else.  It is 26-neighbour local: a B voxel goes iff its segment
+ *   is flagged; a node voxel with deg 1 goes iff its single neighbour is a B voxel of a flagged segment.  A path between two end nodes
+ *   is kept, cycles are kept, nodes of kind 2 are never touched.  Each removal is a chain of simple-point deletions from the tip, so
+ *   the 26-components and the Euler characteristic of S are unchanged.
+ *
+ * vg_skelgraph_classify: one pass over skel writes degree (as vg_neighbour_count26), segment_mask (1 on B) and node_mask (1 on N), each
+ *   uint8[n]; none may overlap skel.  One launch; 32-bit loads and stores, four voxels a lane, where Z % 4 == 0 and the four pointers
+ *   are 4-byte aligned, bytes otherwise.
+ * vg_skelgraph_scratch_bytes(E, V): the scratch of vg_skelgraph_tables, al16(80 (E + 1) + 36 (V + 1) + 16) + al16(12 (E + 1)) bytes.
+ * vg_skelgraph_tables: the tables above from skel, degree, and the two label volumes (int32[n]) with their counts E and V (each
+ *   0 .. n / 2 + 1).  Every table has E + 1 (V + 1) rows, row 0 zeros: seg_half_steps int64 [E + 1][7], seg_voxels int32, seg_ends int64
+ *   [E + 1][2], seg_nodes int32 [E + 1][2], seg_length and seg_chord fp64; with radius_or_null (then both or neither of) seg_radius_mean
+ *   fp64 [E + 1] and seg_radius_minmax fp32 [E + 1][2]; node_voxels, node_degree int32, node_kind uint8, node_centroid fp64 [V + 1][3].
+ *   bad2 = (voxels with a skipped radius, labels met outside 0 .. E / 0 .. V -- such a label is never used as an index).  sampling3 =
+ *   three doubles IN HOST MEMORY, read before the call returns, each finite and > 0.  fp64 / int64 tables are 8-byte aligned, 32-bit
+ *   ones 4-byte; scratch 16-byte aligned, contents irrelevant on entry.  Two memsets and two launches: one thread per voxel (a wave
+ *   without foreground leaves after one load; a wave whose segment voxels lie in one segment, or whose node voxels lie in one node,
+ *   adds its lanes up before one lane issues the atomics), then one thread per segment and per node.
+ * vg_skelgraph_prune: out (uint8[n], 0 / 1) = S after one pruning round with min_length (not a NaN) under sampling3; reads the
+ *   seg_half_steps, seg_nodes and node_kind that vg_skelgraph_tables wrote.  flags: E + 1 bytes of scratch (1 per spur).  counts2 =
+ *   (spurs, voxels deleted).  out must not overlap an input.  One memset and two launches.
+ * --------------------------------------------------------------------------------------------- */
+int vg_skelgraph_classify(const uint8_t* skel, int X, int Y, int Z, uint8_t* degree, uint8_t* segment_mask, uint8_t* node_mask, vg_stream_t stream);
+int64_t vg_skelgraph_scratch_bytes(int E, int V);
+int vg_skelgraph_tables(const uint8_t* skel, const uint8_t* degree, const int32_t* segment_labels, const int32_t* node_labels,
+                        const float* radius_or_null, int X, int Y, int Z, int E, int V, const double* sampling3_or_null,
+                        int64_t* seg_half_steps, int32_t* seg_voxels, int64_t* seg_ends, int32_t* seg_nodes, double* seg_length, double* seg_chord,
+                        double* seg_radius_mean_or_null, float* seg_radius_minmax_or_null, int32_t* node_voxels, int32_t* node_degree,
+                        uint8_t* node_kind, double* node_centroid, uint32_t* bad2, void* scratch, int64_t scratch_bytes, vg_stream_t stream);
+int vg_skelgraph_prune(const uint8_t* skel, const uint8_t* degree, const int32_t* segment_labels, const int32_t* node_labels, int X, int Y, int Z,
+                       int E, int V, const int64_t* seg_half_steps, const int32_t* seg_nodes, const uint8_t* node_kind, double min_length,
+                       const double* sampling3_or_null, uint8_t* flags, uint8_t* out, uint32_t* counts2, vg_stream_t stream);
+
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */
 int vg_memset_zero(void* p, int64_t nbytes, vg_stream_t stream);

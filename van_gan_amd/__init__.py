@@ -12,3 +12,4 @@ from .preprocess import (lanczos4_table, median_filter, order_stats, outlier_lim
 from .postprocess import binarise_prediction, histogram256, label_components, remove_small_objects, vessel_mask  # noqa: F401
 from .postprocess import distance_transform_edt, fill_holes, vessel_radius  # noqa: F401
 from .postprocess import skeleton_nodes, skeletonize, vessel_centreline  # noqa: F401
+from .postprocess import SkeletonGraph, network_summary, prune_spurs, skeleton_graph, vessel_graph  # noqa: F401

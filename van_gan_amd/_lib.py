@@ -162,6 +162,10 @@ _SIGS = {
     'vg_skeleton_passes': ([c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p], c_int),
     'vg_skeleton_end': ([c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p], c_int),
     'vg_neighbour_count26': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
+    'vg_skelgraph_classify': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_skelgraph_scratch_bytes': ([c_int, c_int], c_i64),
+    'vg_skelgraph_tables': ([c_void_p] * 5 + [c_int] * 5 + [c_void_p] * 14 + [c_void_p, c_i64, c_void_p], c_int),
+    'vg_skelgraph_prune': ([c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 3 + [C.c_double] + [c_void_p] * 5, c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

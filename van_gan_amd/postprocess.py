@@ -6,7 +6,9 @@ arithmetic runs in csrc/vg_components.hip (include/vangan_hip.h "Prediction post
 buffers and checks.  Then what measures that network, at the end of the file: the exact Euclidean distance transform
 (scipy.ndimage.distance_transform_edt), hole filling (scipy.ndimage.binary_fill_holes) and the vessel radius, the two chained
 (csrc/vg_edt.hip).  Then its centreline: exact topological thinning to a one-voxel-wide curve skeleton, the
-degree of every skeleton voxel, and the radius along the centreline (csrc/vg_skeleton.hip).
+degree of every skeleton voxel, and the radius along the centreline (csrc/vg_skeleton.hip).  Then the graph of
+that centreline: segments and nodes with length, chord and radius per segment, the pruning of short spurs and a summary of the network
+(csrc/vg_skelgraph.hip); skeleton_graph reads the two counts back once to size its tables.
 
 A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost, a contiguous torch tensor ON THE DEVICE: a prediction is fp32, a mask uint8 or bool
 (0 is background).  Arguments are checked before the device is touched (ValueError).  Every function only enqueues unless a read-back
@@ -448,3 +450,195 @@ def vessel_centreline(mask, sampling=None, fill: bool = True):
         skel = _thin(m, shape, None)[0]
         radius = _edt(m, shape, s, False)
         return skel, torch.where(skel != 0, radius, torch.zeros((), dtype=radius.dtype, device=radius.device))
+
+
+# ------------------------------------------------------------------------------------------------ the vessel graph (csrc/vg_skelgraph.hip)
+NODE_ISOLATED, NODE_END, NODE_OTHER = 0, 1, 2      # node_kind
+
+
+class SkeletonGraph:
+    """The graph of a skeleton as device tensors (include/vangan_hip.h "The vessel graph" has the definitions).  segment_labels and
+    node_labels: int32 [X,Y,Z], 1 .. E on the voxels with two neighbours, 1 .. V on every other foreground voxel, numbered as
+    scipy.ndimage.label numbers them; degree: uint8 [X,Y,Z], skeleton_nodes of the input.  E, V: ints.  Tables with E + 1 rows, row 0
+    zeros: seg_voxels int32, seg_nodes int32 [.,2], seg_ends int64 [.,2] (linear indices, -1 for a cycle), seg_half_steps int64 [.,7],
+    seg_length and seg_chord fp64; seg_radius_mean fp64, seg_radius_min / _max fp32 when a radius was given, else None.  Tables with
+    V + 1 rows: node_voxels, node_degree int32, node_kind uint8 (NODE_ISOLATED, NODE_END, NODE_OTHER), node_centroid fp64 [.,3].
+    shape, sampling: the (X, Y, Z) of the volume and the three spacings the lengths are in."""
+    FIELDS = ('segment_labels', 'node_labels', 'degree', 'E', 'V', 'seg_voxels', 'seg_nodes', 'seg_ends', 'seg_half_steps', 'seg_length', 'seg_chord',
+              'seg_radius_mean', 'seg_radius_min', 'seg_radius_max', 'node_voxels', 'node_degree', 'node_kind', 'node_centroid', 'shape', 'sampling')
+
+    def __init__(self, **fields):
+        assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return 'SkeletonGraph(E=%d, V=%d, shape=%s, sampling=%s)' % (self.E, self.V, self.shape, self.sampling)
+
+
+def _graph_volume(skel):
+    """A skeleton (or any mask) whose two classes of voxels are going to be labelled."""
+    m, shape = _device_volume(skel, (torch.uint8, torch.bool), 'skel', labelled=True)
+    return (m.view(torch.uint8) if m.dtype == torch.bool else m), shape
+
+
+def _s3(s):
+    return None if s is None else (ctypes.c_double * 3)(*s)               # host memory, read before the call returns
+
+
+def _graph(m: torch.Tensor, shape, radius, s) -> SkeletonGraph:
+    dev = m.device
+    X, Y, Z = shape
+    deg, bm, nm = (torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(3))
+    _check(lib.vg_skelgraph_classify(_p(m), X, Y, Z, _p(deg), _p(bm), _p(nm), stream()), 'vg_skelgraph_classify')
+    seg_labels, _, res_b = _label(bm, shape, 3)
+    node_labels, _, res_n = _label(nm, shape, 3)
+    host = [int(w) for w in torch.cat([res_b, res_n]).cpu()]              # the one read-back that sizes the tables
+    if host[R_STATUS] != 0 or host[4 + R_STATUS] != 0:
+        raise RuntimeError('vg_cc_label reported status %d (segments), %d (nodes)' % (host[R_STATUS], host[4 + R_STATUS]))
+    E, V = host[R_K], host[4 + R_K]
+
+    def table(rows, dtype, *cols):
+        return torch.empty((rows + 1,) + cols, dtype=dtype, device=dev)
+    half, vox, ends, nodes = table(E, torch.int64, 7), table(E, torch.int32), table(E, torch.int64, 2), table(E, torch.int32, 2)
+    length, chord = table(E, torch.float64), table(E, torch.float64)
+    rmean = None if radius is None else table(E, torch.float64)
+    rminmax = None if radius is None else table(E, torch.float32, 2)
+    nvox, ndeg, kind, centroid = table(V, torch.int32), table(V, torch.int32), table(V, torch.uint8), table(V, torch.float64, 3)
+    bad = torch.empty(2, dtype=torch.int32, device=dev)
+    scratch, nbytes = _scratch('vg_skelgraph_scratch_bytes', E, V, dev=dev)
+    _check(lib.vg_skelgraph_tables(_p(m), _p(deg), _p(seg_labels), _p(node_labels), None if radius is None else _p(radius), X, Y, Z, E, V, _s3(s),
+                                   _p(half), _p(vox), _p(ends), _p(nodes), _p(length), _p(chord), None if rmean is None else _p(rmean),
+                                   None if rminmax is None else _p(rminmax), _p(nvox), _p(ndeg), _p(kind), _p(centroid), _p(bad), _p(scratch), nbytes,
+                                   stream()), 'vg_skelgraph_tables')
+    if radius is not None:
+        nbad = [int(w) for w in bad.cpu()]
+        if nbad[0] or nbad[1]:
+            raise RuntimeError('skeleton_graph: %d voxels of the skeleton have a radius that is negative, not finite or above the diagonal of the '
+                               'volume (%d labels out of range)' % (nbad[0], nbad[1]))
+    return SkeletonGraph(segment_labels=seg_labels, node_labels=node_labels, degree=deg, E=E, V=V, seg_voxels=vox, seg_nodes=nodes, seg_ends=ends,
+                         seg_half_steps=half, seg_length=length, seg_chord=chord, seg_radius_mean=rmean,
+                         seg_radius_min=None if rminmax is None else rminmax[:, 0], seg_radius_max=None if rminmax is None else rminmax[:, 1],
+                         node_voxels=nvox, node_degree=ndeg, node_kind=kind, node_centroid=centroid, shape=tuple(shape),
+                         sampling=(1.0, 1.0, 1.0) if s is None else s)
+
+
+def skeleton_graph(skel, radius=None, sampling=None) -> SkeletonGraph:
+    """The graph of a skeleton (uint8 / bool [X,Y,Z] on the device; any mask is legal) as a SkeletonGraph: the voxels with exactly two
+    26-neighbours form the segments, every other voxel the nodes (a cluster of adjacent junction voxels is one node), both numbered as
+    scipy.ndimage.label numbers them; per segment its voxels, its two end nodes and end voxels, its exact length under sampling (None,
+    a number or three: the voxel spacing along X, Y, Z), the chord between its ends, and with radius (fp32 [X,Y,Z], such as vessel_radius
+    or vessel_centreline returns) the mean, min and max radius along it; per node its voxels, attachments, kind and centroid.  Every
+    number is a function of the input alone, bit for bit (integer atomics only).  Reads the two counts back once to size the tables
+    (RuntimeError on a non-zero status of the labelling), and with a radius one more word: RuntimeError when a voxel of a segment has a
+    radius that is negative, NaN, infinite or above the diagonal of the volume.  An empty mask gives E = V = 0 and tables of their zero
+    row.  Temporary device memory: that of label_components, beside the two label volumes and three bytes per voxel."""
+    s = _sampling(sampling)
+    m, shape = _device_volume(skel, (torch.uint8, torch.bool), 'skel', labelled=True, check_device=False)
+    r = None
+    if radius is not None:
+        r, rshape = _device_volume(radius, (torch.float32,), 'radius', check_device=False)
+        if rshape != shape:
+            raise ValueError('radius has shape %s, skel %s' % (rshape, shape))
+    _on_device(m, 'skel')
+    if r is not None:
+        _on_device(r, 'radius')
+        if r.device != m.device:
+            raise ValueError('radius is on %s, skel on %s' % (r.device, m.device))
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    with torch.cuda.device(m.device):
+        return _graph(m, shape, r, s)
+
+
+def _min_length(min_length, what='min_length') -> float:
+    if isinstance(min_length, bool) or not isinstance(min_length, numbers.Real) or math.isnan(min_length):
+        raise ValueError('%s is a number (a length in the units of the sampling), got %r' % (what, min_length))
+    return float(min_length)
+
+
+def _rounds(rounds) -> int:
+    try:
+        k = operator.index(rounds)
+    except TypeError:
+        raise ValueError('rounds is an integer >= 1, got %r' % (rounds,)) from None
+    if isinstance(rounds, bool) or k < 1:
+        raise ValueError('rounds is an integer >= 1, got %r' % (rounds,))
+    return k
+
+
+def _prune_round(m: torch.Tensor, g: SkeletonGraph, min_length: float, s):
+    """(mask, counts2) of one pruning round of the uint8 device mask m whose graph is g."""
+    X, Y, Z = g.shape
+    out = torch.empty(g.shape, dtype=torch.uint8, device=m.device)
+    flags = torch.empty(g.E + 1, dtype=torch.uint8, device=m.device)
+    counts = torch.empty(2, dtype=torch.int32, device=m.device)
+    _check(lib.vg_skelgraph_prune(_p(m), _p(g.degree), _p(g.segment_labels), _p(g.node_labels), X, Y, Z, g.E, g.V, _p(g.seg_half_steps), _p(g.seg_nodes),
+                                  _p(g.node_kind), min_length, _s3(s), _p(flags), _p(out), _p(counts), stream()), 'vg_skelgraph_prune')
+    return out, counts
+
+
+def prune_spurs(skel, min_length, sampling=None, rounds=1, return_info: bool = False):
+    """skel (uint8 / bool [X,Y,Z] on the device) without its short spurs, uint8 (0 / 1): a spur is a segment between an end point and a
+    node that is none, shorter than min_length (in the units of sampling); a round deletes the voxels of every spur and the end voxel
+    it hangs from, and nothing else -- the connected components and the Euler characteristic stay, a segment between two end points
+    and every cycle stay.  Each of up to `rounds` rounds is a skeleton_graph of what the round before left (removing a spur can turn
+    its junction into a voxel of a longer segment, which the next round may find to be a spur) and one launch pair; with rounds > 1 or
+    return_info the two counts of each round are read back and the rounds stop after one that removed nothing.  return_info=True:
+    (mask, dict(rounds, spurs, voxels)) -- the rounds run and the spurs and voxels each removed.  min_length <= 0 returns a copy."""
+    ml = _min_length(min_length)
+    k = _rounds(rounds)
+    s = _sampling(sampling)
+    m, shape = _graph_volume(skel)
+    info = dict(rounds=0, spurs=[], voxels=[])
+    with torch.cuda.device(m.device):
+        cur = m
+        if ml > 0.0:
+            for _ in range(k):
+                cur, counts = _prune_round(cur, _graph(cur, shape, None, s), ml, s)
+                info['rounds'] += 1
+                if k > 1 or return_info:
+                    c = [int(w) for w in counts.cpu()]
+                    info['spurs'].append(c[0])
+                    info['voxels'].append(c[1])
+                    if c[1] == 0:
+                        break
+        out = (m != 0).to(torch.uint8) if cur is m else cur
+    return (out, info) if return_info else out
+
+
+def network_summary(graph: SkeletonGraph) -> dict:
+    """Numbers about the network of a SkeletonGraph, as a dict on the host (one read-back of the tables): segments, cycles (closed
+    segments without a node), loops (both ends at one node), nodes, end_points, junctions (the nodes of kind NODE_OTHER), isolated
+    (voxels on their own), total_length, length_density (total length per unit volume, the volume being that of the whole array under
+    the sampling), mean_radius (weighted by the voxels of the segments; None without a radius) and mean_tortuosity (the mean of
+    length / chord over the segments with chord > 0; None where there is none)."""
+    if not isinstance(graph, SkeletonGraph):
+        raise ValueError('network_summary takes a SkeletonGraph, got %s' % type(graph).__name__)
+    g = graph
+    has_r = g.seg_radius_mean is not None
+    cols = [g.seg_length, g.seg_chord, g.seg_voxels.double(), g.seg_nodes[:, 0].double(), g.seg_nodes[:, 1].double(), g.seg_ends[:, 0].double()]
+    if has_r:
+        cols.append(g.seg_radius_mean)
+    host = torch.cat(cols + [g.node_kind.double()]).cpu().numpy()         # every integer here is below 2^31: exact in fp64
+    E1 = g.E + 1
+    length, chord, vox, n0, n1, e0 = (host[i * E1 + 1:(i + 1) * E1] for i in range(6))
+    kind = host[len(cols) * E1 + 1:]
+    total = float(length.sum())
+    volume = math.prod(g.shape) * math.prod(g.sampling)
+    curved = chord > 0
+    return dict(segments=g.E, cycles=int((e0 < 0).sum()), loops=int(((n0 == n1) & (n0 > 0)).sum()), nodes=g.V,
+                end_points=int((kind == NODE_END).sum()), junctions=int((kind == NODE_OTHER).sum()), isolated=int((kind == NODE_ISOLATED).sum()),
+                total_length=total, length_density=total / volume,
+                mean_radius=(float((host[6 * E1 + 1:7 * E1] * vox).sum() / vox.sum()) if has_r and vox.sum() > 0 else None),
+                mean_tortuosity=float((length[curved] / chord[curved]).mean()) if curved.any() else None)
+
+
+def vessel_graph(mask, sampling=None, fill: bool = True, min_spur=0.0):
+    """(skeleton, graph): vessel_centreline(mask, sampling, fill), then prune_spurs(skeleton, min_spur, sampling) when min_spur > 0, then
+    skeleton_graph of the skeleton with the radius map along it -- the network of a vessel mask with length and radius per vessel.
+    A volume without any background voxel has an infinite radius, which skeleton_graph refuses."""
+    s = _sampling(sampling)
+    ms = _min_length(min_spur, 'min_spur')
+    skel, radius = vessel_centreline(mask, s, fill)
+    if ms > 0.0:
+        skel = prune_spurs(skel, ms, s)
+    return skel, skeleton_graph(skel, radius, s)

@@ -1000,6 +1000,17 @@ class VanGan:
             return postprocess.vessel_mask(pred, threshold, min_size, connectivity, return_info, fill_holes=fill_holes, skeleton=True)
         return postprocess.vessel_mask(pred, threshold, min_size, connectivity, return_info, fill_holes=fill_holes)
 
+    def segment_graph(self, gen: str, raw, subvol_size=None, *, sampling=None, min_spur=0.0, threshold=127.5, min_size=64, connectivity=3, **kw):
+        """Raw volume -> (skeleton, graph) on the device: segment_mask(gen, raw, subvol_size, fill_holes=True, ...) followed by
+        postprocess.vessel_graph(mask, sampling, fill=False, min_spur) -- the centreline of the vascular network (uint8 [X,Y,Z]) and its
+        SkeletonGraph: segments and nodes with length, chord and radius per segment, in the units of sampling (the voxel spacing along
+        X, Y, Z).  min_spur > 0 removes the terminal spurs shorter than that first.  The arguments of the post-processing are checked
+        before anything runs."""
+        from . import postprocess
+        postprocess._sampling(sampling), postprocess._min_length(min_spur, 'min_spur')
+        mask = self.segment_mask(gen, raw, subvol_size, threshold=threshold, min_size=min_size, connectivity=connectivity, fill_holes=True, **kw)
+        return postprocess.vessel_graph(mask, sampling, fill=False, min_spur=min_spur)
+
     # ------------------------------------------------------------------------------------------------
     def save_checkpoint(self, epoch: int):
         """vangan.py:247-250 (own format: the TF tensor-bundle format is not readable without TF).  The replicas hold identical
