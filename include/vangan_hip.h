@@ -919,6 +919,61 @@ int vg_skelgraph_prune(const uint8_t* skel, const uint8_t* degree, const int32_t
                        int E, int V, const int64_t* seg_half_steps, const int32_t* seg_nodes, const uint8_t* node_kind, double min_length,
                        const double* sampling3_or_null, uint8_t* flags, uint8_t* out, uint32_t* counts2, vg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scoring a mask (csrc/vg_evaluate.hip; van_gan_amd/postprocess.py overlap_counts, mask_surface,
+ * euler_characteristic, betti_numbers, surface_distances, cldice_score, evaluate_segmentation): what measures a segmentation against a
+ * ground truth -- overlap, topology, surface distances.  The same code in both storage builds.  Volumes are [X][Y][Z] with Z innermost,
+ * n = X * Y * Z, 1 <= n < 2^31; masks are uint8, foreground is != 0.  Every entry only enqueues, allocates nothing, checks its arguments
+ * on the host before any launch (VG_EINVAL, nothing launched: NULL pointers, those named _or_null excepted; n or an extent out of range;
+ * a pointer that is not aligned for its type; a scratch smaller than its query says or not 16-byte aligned; what is listed per entry)
+ * and initialises its own outputs: no result depends on what a buffer held before.  Only integer atomics, each a sum -- no float atomic
+ * appears in the file: equal inputs give bit-identical results on every run.  No workgroup waits on another, and every loop is a grid
+ * stride over a count fixed at launch.
+ *
+ * vg_mask_counts: counts4 (uint64[4], 8-byte aligned) = (|a & b|, |a & !b|, |!a & b|, |!a & !b|) of the two masks of n voxels; with a the
+ *   prediction and b the truth that is (tp, fp, fn, tn).  A memset and one launch: 16-byte loads where a and b are equally far from a
+ *   16-byte boundary (the voxels before it and after the last whole vector go one a lane), single voxels otherwise; a sum per wave, then
+ *   one atomic per workgroup and counter.
+ * vg_mask_surface: surf[v] = mask[v] != 0 && (a face neighbour of v is 0 or lies outside the volume) (0 / 1) -- the mask without
+ *   scipy.ndimage.binary_erosion(mask, generate_binary_structure(3, 1), border_value=0) -- and not_surf[v] = !surf[v], the mask whose
+ *   vg_edt is the distance to the nearest surface voxel; either may be NULL.  *count (uint64, 8-byte aligned) = the surface voxels.
+ *   A memset and one launch; 32-bit loads and stores, four voxels a lane in packed arithmetic, where Z % 4 == 0 and the three pointers
+ *   are 4-byte aligned, bytes otherwise.  surf and not_surf must overlap neither mask nor each other.
+ * vg_euler_characteristic: cells5 (int64[5], 8-byte aligned) = (V, E, F, C, V - E + F - C) of the closed cubical complex of the
+ *   foreground: C the foreground voxels, and a face / edge / vertex of the voxel grid counted once when any of the 2 / 4 / 8 voxels that
+ *   share it is foreground, voxels outside the volume being background.  V - E + F - C is the Euler characteristic of the foreground
+ *   under 26-connectivity with a 6-connected background, the convention of vg_skeleton_*.  A memset and one launch over the
+ *   (X + 1)(Y + 1)(Z + 1) corners, each thread counting the cells at the low corner of its voxel; the same two forms as vg_mask_surface.
+ * vg_flags_count: out[0] (uint32) = the labels l in 1 .. K with flags[l] == 0, K = result4[0] read on the device and capped at n / 2 + 1,
+ *   the last label the n / 2 + 2 bytes of flags have room for.  With labels = vg_cc_label of the INVERTED mask at connectivity 1, result4
+ *   its result and flags from vg_fill_holes_mark, that is the number of enclosed cavities.  A memset and one launch.
+ * vg_masked_stats: statistics of the 32-bit array keys[n] over the voxels with sel[v] != 0 (sel: uint8[n]).  kind VG_EVAL_SQ_I32: keys
+ *   are non-negative int32 squared distances, value = sqrt((double)key), correctly rounded; VG_EVAL_DIST_F32: non-negative finite fp32,
+ *   value = (double)key.  In both the order of the values is the order of the bit patterns as uint32, which is what is selected on.
+ *   out: VG_EVAL_STATS_BYTES bytes on the device, 8-byte aligned: uint64 m, the selected count | uint32 the largest selected key |
+ *   uint32 0 | fp64 sum of the values | uint32 stat[VG_EVAL_MAX_STATS]: stat[r], r < R, is the key of rank max(ceil(q[r] m) - 1, 0) among
+ *   the selected keys in ascending order, product and ceiling in fp64 on the device from m (stat[r] = 0 for r >= R).  m == 0 gives
+ *   maximum, sum and stats 0.  q_host: R doubles IN HOST MEMORY, read before the call returns, 0 < q <= 1; 1 <= R <= VG_EVAL_MAX_STATS.
+ *   The sum: every thread adds its values in index order, a fixed tree of eight levels adds the 256 threads of a workgroup, the
+ *   workgroup's partial goes to the scratch, and one workgroup adds the partials -- thread t those of workgroups t, t + 256, ... in
+ *   ascending order, then the same tree.  The select: the most-significant-digit radix select of vg_order_stats, 8 bits a pass -- a
+ *   histogram kernel over the selected keys that share the prefix, a one-workgroup pick -- without any read-back.  Ten launches
+ *   whatever the data.  scratch: vg_masked_stats_scratch_bytes(n, R) bytes, 16-byte aligned, contents irrelevant on entry.  16-byte loads
+ *   of the keys with 32-bit loads of sel where the two pointers allow, as vg_mask_counts.
+ * --------------------------------------------------------------------------------------------- */
+#define VG_EVAL_SQ_I32 0
+#define VG_EVAL_DIST_F32 1
+#define VG_EVAL_MAX_STATS 4
+#define VG_EVAL_STATS_BYTES 40
+int vg_mask_counts(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* counts4, vg_stream_t stream);
+int vg_mask_surface(const uint8_t* mask, int X, int Y, int Z, uint8_t* surf_or_null, uint8_t* not_surf_or_null, uint64_t* count,
+                    vg_stream_t stream);
+int vg_euler_characteristic(const uint8_t* mask, int X, int Y, int Z, int64_t* cells5, vg_stream_t stream);
+int vg_flags_count(const uint8_t* flags, const uint32_t* result4, int64_t n, uint32_t* out, vg_stream_t stream);
+int64_t vg_masked_stats_scratch_bytes(int64_t n, int R);
+int vg_masked_stats(const void* keys, const uint8_t* sel, int64_t n, int kind, const double* q_host, int R, void* out, void* scratch,
+                    int64_t scratch_bytes, vg_stream_t stream);
+
 /* Device memset-to-zero / device-to-device copy on an explicit stream (hipMemsetAsync / hipMemcpyAsync): what a recorded launch list
  * (van_gan_amd.VanGan.record_train_step) replays in place of torch's zero_() / copy_(), which would go to torch's current stream. */
 int vg_memset_zero(void* p, int64_t nbytes, vg_stream_t stream);

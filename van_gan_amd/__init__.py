@@ -13,3 +13,5 @@ from .postprocess import binarise_prediction, histogram256, label_components, re
 from .postprocess import distance_transform_edt, fill_holes, vessel_radius  # noqa: F401
 from .postprocess import skeleton_nodes, skeletonize, vessel_centreline  # noqa: F401
 from .postprocess import SkeletonGraph, network_summary, prune_spurs, skeleton_graph, vessel_graph  # noqa: F401
+from .postprocess import (SegmentationScores, betti_numbers, cldice_score, euler_characteristic, evaluate_segmentation, mask_surface,  # noqa: F401
+                          overlap_counts, surface_distances)

@@ -166,6 +166,12 @@ _SIGS = {
     'vg_skelgraph_scratch_bytes': ([c_int, c_int], c_i64),
     'vg_skelgraph_tables': ([c_void_p] * 5 + [c_int] * 5 + [c_void_p] * 14 + [c_void_p, c_i64, c_void_p], c_int),
     'vg_skelgraph_prune': ([c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 3 + [C.c_double] + [c_void_p] * 5, c_int),
+    'vg_mask_counts': ([c_void_p, c_void_p, c_i64, c_void_p, c_void_p], c_int),
+    'vg_mask_surface': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    'vg_euler_characteristic': ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
+    'vg_flags_count': ([c_void_p, c_void_p, c_i64, c_void_p, c_void_p], c_int),
+    'vg_masked_stats_scratch_bytes': ([c_i64, c_int], c_i64),
+    'vg_masked_stats': ([c_void_p, c_void_p, c_i64, c_int, C.POINTER(C.c_double), c_int, c_void_p, c_void_p, c_i64, c_void_p], c_int),
     'vg_axpby': ([c_void_p, c_float, c_void_p, c_float, c_i64, c_void_p, c_int, c_void_p], c_int),
     'vg_adam_clip': ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_float, c_float,
                       c_float, c_float, c_float, c_float, c_void_p], c_int),

@@ -8,7 +8,9 @@ buffers and checks.  Then what measures that network, at the end of the file: th
 (csrc/vg_edt.hip).  Then its centreline: exact topological thinning to a one-voxel-wide curve skeleton, the
 degree of every skeleton voxel, and the radius along the centreline (csrc/vg_skeleton.hip).  Then the graph of
 that centreline: segments and nodes with length, chord and radius per segment, the pruning of short spurs and a summary of the network
-(csrc/vg_skelgraph.hip); skeleton_graph reads the two counts back once to size its tables.
+(csrc/vg_skelgraph.hip); skeleton_graph reads the two counts back once to size its tables.  Last, what says how
+good a mask is against a ground truth: overlap, clDice, Betti numbers and Euler characteristic, surface distances
+(csrc/vg_evaluate.hip); evaluate_segmentation enqueues all of it and reads one small block back.
 
 A volume is [X,Y,Z] (or [X,Y,Z,1]) with Z innermost, a contiguous torch tensor ON THE DEVICE: a prediction is fp32, a mask uint8 or bool
 (0 is background).  Arguments are checked before the device is touched (ValueError).  Every function only enqueues unless a read-back
@@ -21,6 +23,7 @@ import ctypes
 import math
 import numbers
 import operator
+import struct
 from typing import Tuple
 
 import torch
@@ -642,3 +645,327 @@ def vessel_graph(mask, sampling=None, fill: bool = True, min_spur=0.0):
     if ms > 0.0:
         skel = prune_spurs(skel, ms, s)
     return skel, skeleton_graph(skel, radius, s)
+
+
+# ------------------------------------------------------------------------------------------------ scoring the mask (csrc/vg_evaluate.hip)
+EVAL_SQ_I32, EVAL_DIST_F32 = 0, 1          # VG_EVAL_SQ_I32, VG_EVAL_DIST_F32
+EVAL_MAX_STATS, EVAL_STATS_BYTES = 4, 40   # VG_EVAL_MAX_STATS, VG_EVAL_STATS_BYTES
+
+
+class SegmentationScores:
+    """What evaluate_segmentation returns, all on the host.  The integers: shape, voxels; tp, fp, fn, tn (pred & truth, pred & !truth,
+    !pred & truth, neither).  From them, in fp64: dice = 2 tp / (2 tp + fp + fn), iou = tp / (tp + fp + fn), precision = tp / (tp + fp),
+    recall = tp / (tp + fn), specificity = tn / (tn + fp), accuracy = (tp + tn) / voxels.  With cldice: skeleton_pred, skeleton_truth (the
+    voxels of the two skeletons), skeleton_pred_in_truth, skeleton_truth_in_pred, tprec = skeleton_pred_in_truth / skeleton_pred, tsens =
+    skeleton_truth_in_pred / skeleton_truth, cldice = 2 tprec tsens / (tprec + tsens).  With topology: betti_pred, betti_truth ((b0, b1,
+    b2): 26-components, tunnels, cavities; b1 = b0 + b2 - euler), euler_pred, euler_truth, betti_error (the three absolute differences)
+    and euler_error.  With surface: surface_pred, surface_truth (the surface voxels), pred_to_truth and truth_to_pred (dict(count,
+    max_key, percentile_key, max, mean, percentile): over the surface voxels of the first mask, the distance to the surface of the
+    second -- the two keys are the device's integers, a squared distance without sampling and the bits of an fp32 distance with it,
+    and value(key) is sqrt(key) or that fp32 number; max = value(max_key), mean = sum / count, percentile = value(percentile_key), the key of
+    rank max(ceil(percentile / 100 * count) - 1, 0)), hausdorff = max of the two max, hausdorff_percentile = max of the two percentile,
+    assd = (sum + sum) / (count + count), and the percentile and sampling they were taken with.  A part that was not asked for is None.
+    Both masks empty: dice = iou = precision = recall = cldice = tprec = tsens = 1 and every distance is 0.  Exactly one empty: those are 0
+    and every distance is inf.  Any other ratio 0 / 0 -- specificity without a negative, cldice of two masks whose skeletons miss each other
+    entirely -- is nan."""
+    FIELDS = ('shape', 'voxels', 'tp', 'fp', 'fn', 'tn', 'dice', 'iou', 'precision', 'recall', 'specificity', 'accuracy',
+              'skeleton_pred', 'skeleton_truth', 'skeleton_pred_in_truth', 'skeleton_truth_in_pred', 'tprec', 'tsens', 'cldice',
+              'betti_pred', 'betti_truth', 'euler_pred', 'euler_truth', 'betti_error', 'euler_error',
+              'surface_pred', 'surface_truth', 'pred_to_truth', 'truth_to_pred', 'hausdorff', 'hausdorff_percentile', 'assd', 'percentile', 'sampling')
+
+    def __init__(self, **fields):
+        assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
+        self.__dict__.update(fields)
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __repr__(self):
+        return 'SegmentationScores(shape=%s, dice=%r, cldice=%r, hausdorff=%r)' % (self.shape, self.dice, self.cldice, self.hausdorff)
+
+
+def _percentile(percentile) -> float:
+    if isinstance(percentile, bool) or not isinstance(percentile, numbers.Real) or not (0.0 < percentile <= 100.0):
+        raise ValueError('percentile is a number in (0, 100], got %r' % (percentile,))
+    return float(percentile)
+
+
+def _score_volume(mask, what: str, labelled: bool = False):
+    m, shape = _device_volume(mask, (torch.uint8, torch.bool), what, labelled=labelled)
+    return (m.view(torch.uint8) if m.dtype == torch.bool else m), shape
+
+
+def _score_pair(pred, truth, labelled: bool = False, distances: bool = False):
+    """(pred, truth, shape) as uint8 device volumes of one shape on one device."""
+    p, shape = _device_volume(pred, (torch.uint8, torch.bool), 'pred', labelled=labelled, check_device=False)
+    t, tshape = _device_volume(truth, (torch.uint8, torch.bool), 'truth', labelled=labelled, check_device=False)
+    if tshape != shape:
+        raise ValueError('truth has shape %s, pred %s' % (tshape, shape))
+    if distances and sum(d * d for d in shape) >= 2 ** 31:
+        raise ValueError('pred of shape %s: the distance transform serves X^2 + Y^2 + Z^2 < 2^31' % (shape,))
+    _on_device(p, 'pred')
+    _on_device(t, 'truth')
+    if t.device != p.device:
+        raise ValueError('truth is on %s, pred on %s' % (t.device, p.device))
+    return (p.view(torch.uint8) if p.dtype == torch.bool else p), (t.view(torch.uint8) if t.dtype == torch.bool else t), shape
+
+
+class _Block:
+    """A small zeroed result block on the device, filled by the entries through pointers into it and read back in one copy."""
+
+    def __init__(self, nbytes: int, dev):
+        self.t = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.host = None
+
+    def at(self, off: int) -> int:
+        return self.t.data_ptr() + off
+
+    def put(self, off: int, words: torch.Tensor):
+        """a device-to-device copy of a small tensor into the block (enqueue-only)"""
+        raw = words.contiguous().view(torch.uint8).reshape(-1)
+        self.t[off:off + raw.numel()].copy_(raw)
+
+    def read(self):
+        self.host = self.t.cpu().numpy()                             # the one synchronising read-back
+
+    def get(self, off: int, dtype: str, count: int = 1):
+        return [v.item() for v in self.host[off:off + count * int(dtype[1:])].view(dtype)]
+
+
+def _enqueue_counts(a: torch.Tensor, b: torch.Tensor, blk: _Block, off: int):
+    _check(lib.vg_mask_counts(_p(a), _p(b), a.numel(), blk.at(off), stream()), 'vg_mask_counts')
+
+
+def _enqueue_surface(m: torch.Tensor, shape, blk: _Block, off: int, want_surf: bool = True, want_not: bool = True):
+    """(surf, not_surf) of the uint8 device mask m, the count of surface voxels into the block."""
+    surf = torch.empty(shape, dtype=torch.uint8, device=m.device) if want_surf else None
+    nsurf = torch.empty(shape, dtype=torch.uint8, device=m.device) if want_not else None
+    _check(lib.vg_mask_surface(_p(m), shape[0], shape[1], shape[2], _p(surf), _p(nsurf), blk.at(off), stream()), 'vg_mask_surface')
+    return surf, nsurf
+
+
+TOPOLOGY_BYTES = 80                        # cells5 (40) | result4 of the mask at connectivity 3 (16) | of its inverse at 1 (16) | cavities (4) | 0 (4)
+
+
+def _enqueue_topology(m: torch.Tensor, shape, blk: _Block, off: int):
+    dev, n = m.device, m.numel()
+    _check(lib.vg_euler_characteristic(_p(m), shape[0], shape[1], shape[2], blk.at(off), stream()), 'vg_euler_characteristic')
+    blk.put(off + 40, _label(m, shape, 3)[2])
+    labels, _, result = _label((m == 0).view(torch.uint8), shape, 1)
+    flags = torch.empty(sizes_capacity(n), dtype=torch.uint8, device=dev)
+    _check(lib.vg_fill_holes_mark(_p(labels), shape[0], shape[1], shape[2], _p(flags), stream()), 'vg_fill_holes_mark')
+    _check(lib.vg_flags_count(_p(flags), _p(result), n, blk.at(off + 72), stream()), 'vg_flags_count')
+    blk.put(off + 56, result)
+
+
+def _read_topology(blk: _Block, off: int):
+    """((b0, b1, b2), euler) from the block after its read-back."""
+    cells = blk.get(off, 'i8', 5)
+    fg, bg, b2 = blk.get(off + 40, 'i4', 4), blk.get(off + 56, 'i4', 4), blk.get(off + 72, 'u4')[0]
+    if fg[R_STATUS] != 0 or bg[R_STATUS] != 0:
+        raise RuntimeError('vg_cc_label reported status %d (mask), %d (background)' % (fg[R_STATUS], bg[R_STATUS]))
+    b0, chi = fg[R_K], cells[4]
+    return (b0, b0 + b2 - chi, b2), chi
+
+
+def _enqueue_distances(sel: torch.Tensor, nsurf_other: torch.Tensor, shape, s, q: float, blk: _Block, off: int):
+    """Statistics, over the voxels of sel, of the distance to the nearest zero of nsurf_other."""
+    dev, n = sel.device, sel.numel()
+    keys = _edt(nsurf_other, shape, s, s is None)
+    scratch, nbytes = _scratch('vg_masked_stats_scratch_bytes', n, 1, dev=dev)
+    _check(lib.vg_masked_stats(_p(keys), _p(sel), n, EVAL_SQ_I32 if s is None else EVAL_DIST_F32, (ctypes.c_double * 1)(q), 1, blk.at(off), _p(scratch),
+                               nbytes, stream()), 'vg_masked_stats')
+
+
+def _key_value(key: int, weighted: bool) -> float:
+    """the value of a key of vg_masked_stats: the fp32 number with these bits, or the square root of the integer"""
+    return struct.unpack('<f', struct.pack('<I', key))[0] if weighted else math.sqrt(key)
+
+
+def _read_distances(blk: _Block, off: int, weighted: bool):
+    m, = blk.get(off, 'u8')
+    kmax, = blk.get(off + 8, 'u4')
+    total, = blk.get(off + 16, 'f8')
+    kq, = blk.get(off + 24, 'u4')
+    return dict(count=m, max_key=kmax, percentile_key=kq, max=_key_value(kmax, weighted), mean=total / m if m else 0.0,
+                percentile=_key_value(kq, weighted)), total
+
+
+def _surface_figures(pt, tp, sums) -> dict:
+    """The two directions joined; an empty surface on exactly one side makes every distance infinite."""
+    if (pt['count'] == 0) != (tp['count'] == 0):
+        for d in (pt, tp):
+            d.update(max=math.inf, mean=math.inf, percentile=math.inf)
+        return dict(pred_to_truth=pt, truth_to_pred=tp, hausdorff=math.inf, hausdorff_percentile=math.inf, assd=math.inf)
+    both = pt['count'] + tp['count']
+    return dict(pred_to_truth=pt, truth_to_pred=tp, hausdorff=max(pt['max'], tp['max']), hausdorff_percentile=max(pt['percentile'], tp['percentile']),
+                assd=(sums[0] + sums[1]) / both if both else 0.0)
+
+
+def _ratio(a: int, b: int) -> float:
+    return a / b if b else math.nan
+
+
+def _overlap_figures(tp: int, fp: int, fn: int, tn: int) -> dict:
+    if tp + fp == 0 or tp + fn == 0:                                 # a mask is empty: 1 when both are, else 0
+        v = 1.0 if tp + fp + fn == 0 else 0.0
+        dice = iou = precision = recall = v
+    else:
+        dice, iou, precision, recall = _ratio(2 * tp, 2 * tp + fp + fn), _ratio(tp, tp + fp + fn), _ratio(tp, tp + fp), _ratio(tp, tp + fn)
+    return dict(tp=tp, fp=fp, fn=fn, tn=tn, dice=dice, iou=iou, precision=precision, recall=recall, specificity=_ratio(tn, tn + fp),
+                accuracy=_ratio(tp + tn, tp + fp + fn + tn))
+
+
+def _cldice_figures(sp_in_t: int, sp: int, st_in_p: int, st: int) -> dict:
+    if sp == 0 or st == 0:                                           # a skeleton is empty exactly when its mask is
+        tprec = tsens = cldice = 1.0 if sp + st == 0 else 0.0
+    else:
+        tprec, tsens = sp_in_t / sp, st_in_p / st
+        cldice = 2.0 * tprec * tsens / (tprec + tsens) if tprec + tsens > 0.0 else math.nan
+    return dict(skeleton_pred=sp, skeleton_truth=st, skeleton_pred_in_truth=sp_in_t, skeleton_truth_in_pred=st_in_p, tprec=tprec, tsens=tsens,
+                cldice=cldice)
+
+
+def overlap_counts(pred, truth) -> Tuple[int, int, int, int]:
+    """(tp, fp, fn, tn) of two masks (uint8 / bool [X,Y,Z] on the device, one shape): the voxels in both, in pred alone, in truth alone,
+    in neither, as Python ints.  One launch and one read-back of the four counters."""
+    p, t, _ = _score_pair(pred, truth)
+    with torch.cuda.device(p.device):
+        blk = _Block(32, p.device)
+        _enqueue_counts(p, t, blk, 0)
+        blk.read()
+    return tuple(blk.get(0, 'u8', 4))
+
+
+def mask_surface(mask, return_count: bool = False):
+    """uint8 [X,Y,Z] (0 / 1): the foreground voxels of mask with a face neighbour that is background or outside the volume -- mask &
+    ~scipy.ndimage.binary_erosion(mask, generate_binary_structure(3, 1), border_value=0).  Enqueue-only; return_count=True: (surface,
+    voxels) with the count read back."""
+    m, shape = _score_volume(mask, 'mask')
+    with torch.cuda.device(m.device):
+        blk = _Block(8, m.device)
+        surf, _ = _enqueue_surface(m, shape, blk, 0, want_not=False)
+        if not return_count:
+            return surf
+        blk.read()
+    return surf, blk.get(0, 'u8')[0]
+
+
+def euler_characteristic(mask) -> int:
+    """The Euler characteristic of the foreground of mask (26-connected, background 6-connected, outside the volume background): vertices
+    - edges + faces - cubes of its closed cubical complex, counted on the device; one read-back."""
+    m, shape = _score_volume(mask, 'mask')
+    with torch.cuda.device(m.device):
+        blk = _Block(40, m.device)
+        _check(lib.vg_euler_characteristic(_p(m), shape[0], shape[1], shape[2], blk.at(0), stream()), 'vg_euler_characteristic')
+        blk.read()
+    return blk.get(0, 'i8', 5)[4]
+
+
+def betti_numbers(mask) -> Tuple[int, int, int]:
+    """(b0, b1, b2) of the foreground of mask under the convention of skeletonize: b0 its 26-components (label_components at connectivity
+    3), b2 its cavities -- the 6-components of the background that reach no face of the volume -- and b1 = b0 + b2 - euler_characteristic,
+    its tunnels.  One read-back (RuntimeError on a non-zero status of a labelling).  Temporary device memory as label_components."""
+    m, shape = _score_volume(mask, 'mask', labelled=True)
+    with torch.cuda.device(m.device):
+        blk = _Block(TOPOLOGY_BYTES, m.device)
+        _enqueue_topology(m, shape, blk, 0)
+        blk.read()
+    return _read_topology(blk, 0)[0]
+
+
+def surface_distances(pred, truth, sampling=None, percentile=95.0) -> dict:
+    """The distances between the surfaces (mask_surface) of two masks, as a dict on the host: surface_pred, surface_truth (voxels),
+    pred_to_truth and truth_to_pred, hausdorff, hausdorff_percentile, assd, percentile, sampling -- the fields of SegmentationScores,
+    defined there.  Without sampling the distances are exact: integer squared distances on the device, the square root of each in fp64;
+    with sampling (a number or three, the voxel spacing) they are the fp32 distances of distance_transform_edt.  The sums are fp64, added
+    in a fixed order: equal inputs give equal bits.  The percentile is the nearest-rank one of each direction.  One read-back; the two
+    transforms are enqueued whatever the masks hold, and an empty surface is told from the counts afterwards."""
+    s, q = _sampling(sampling), _percentile(percentile) / 100.0
+    p, t, shape = _score_pair(pred, truth, distances=True)
+    with torch.cuda.device(p.device):
+        blk = _Block(16 + 2 * EVAL_STATS_BYTES, p.device)
+        _enqueue_surfaces_and_distances(p, t, shape, s, q, blk, 0)
+        blk.read()
+    return _read_surfaces_and_distances(blk, 0, s, percentile)
+
+
+def _enqueue_surfaces_and_distances(p, t, shape, s, q, blk: _Block, off: int):
+    """block: surface voxels of pred (8) | of truth (8) | statistics pred -> truth | truth -> pred"""
+    surf_p, nsurf_p = _enqueue_surface(p, shape, blk, off)
+    surf_t, nsurf_t = _enqueue_surface(t, shape, blk, off + 8)
+    _enqueue_distances(surf_p, nsurf_t, shape, s, q, blk, off + 16)
+    _enqueue_distances(surf_t, nsurf_p, shape, s, q, blk, off + 16 + EVAL_STATS_BYTES)
+
+
+def _read_surfaces_and_distances(blk: _Block, off: int, s, percentile) -> dict:
+    pt, sum_pt = _read_distances(blk, off + 16, s is not None)
+    tp, sum_tp = _read_distances(blk, off + 16 + EVAL_STATS_BYTES, s is not None)
+    out = dict(surface_pred=blk.get(off, 'u8')[0], surface_truth=blk.get(off + 8, 'u8')[0])
+    out.update(_surface_figures(pt, tp, (sum_pt, sum_tp)))
+    out.update(percentile=float(percentile), sampling=(1.0, 1.0, 1.0) if s is None else s)
+    return out
+
+
+def _enqueue_cldice(p, t, shape, k, blk: _Block, off: int):
+    """block: counts4 of (skeleton of pred, truth) | counts4 of (skeleton of truth, pred)"""
+    _enqueue_counts(_thin(p, shape, k)[0], t, blk, off)
+    _enqueue_counts(_thin(t, shape, k)[0], p, blk, off + 32)
+
+
+def _read_cldice(blk: _Block, off: int) -> dict:
+    a, b = blk.get(off, 'u8', 4), blk.get(off + 32, 'u8', 4)
+    return _cldice_figures(a[0], a[0] + a[1], b[0], b[0] + b[1])
+
+
+def cldice_score(pred, truth, max_passes=None) -> dict:
+    """The hard clDice of two masks, as a dict on the host: with S = skeletonize of each mask as it is given (no hole filling), tprec =
+    |S_pred & truth| / |S_pred|, tsens = |S_truth & pred| / |S_truth| and cldice = 2 tprec tsens / (tprec + tsens), beside the four
+    integers (the fields of SegmentationScores).  max_passes=None thins until nothing changes, which reads a few words back every four
+    passes, as skeletonize does; max_passes=k runs exactly k passes and is enqueue-only up to the one read-back of the counts."""
+    k = _max_passes(max_passes)
+    p, t, shape = _score_pair(pred, truth)
+    with torch.cuda.device(p.device):
+        blk = _Block(64, p.device)
+        _enqueue_cldice(p, t, shape, k, blk, 0)
+        blk.read()
+    return _read_cldice(blk, 0)
+
+
+def evaluate_segmentation(pred, truth, sampling=None, percentile=95.0, topology: bool = True, surface: bool = True, cldice: bool = True,
+                          max_passes=None) -> SegmentationScores:
+    """Score the mask pred against the ground truth (both uint8 / bool [X,Y,Z] on the device, one shape) without leaving the device:
+    overlap (overlap_counts), and as asked for clDice (cldice_score), the Betti numbers and the Euler characteristic of both masks
+    (betti_numbers) and the surface distances (surface_distances, under sampling and percentile).  Returns a SegmentationScores, where
+    every formula and the degenerate cases are written down.  Every integer is counted on the device; the ratios are formed on the host
+    in fp64 from the integers.  Everything is enqueued first and one small block is read back at the end -- the one synchronising
+    step, except that cldice=True with max_passes=None thins until nothing changes, which reads its counts back every four passes
+    (skeletonize); max_passes=k thins exactly k passes and keeps the call to the one read-back.  RuntimeError on a non-zero status of
+    a labelling.  Needs X^2 + Y^2 + Z^2 < 2^31 with surface=True."""
+    s, q = _sampling(sampling), _percentile(percentile) / 100.0
+    k = _max_passes(max_passes)
+    p, t, shape = _score_pair(pred, truth, labelled=bool(topology), distances=bool(surface))
+    o_cl, o_top, o_surf = 32, 96, 96 + 2 * TOPOLOGY_BYTES
+    with torch.cuda.device(p.device):
+        blk = _Block(o_surf + 16 + 2 * EVAL_STATS_BYTES, p.device)
+        _enqueue_counts(p, t, blk, 0)
+        if cldice:
+            _enqueue_cldice(p, t, shape, k, blk, o_cl)
+        if topology:
+            _enqueue_topology(p, shape, blk, o_top)
+            _enqueue_topology(t, shape, blk, o_top + TOPOLOGY_BYTES)
+        if surface:
+            _enqueue_surfaces_and_distances(p, t, shape, s, q, blk, o_surf)
+        blk.read()
+    f = dict.fromkeys(SegmentationScores.FIELDS)
+    f.update(shape=tuple(shape), voxels=math.prod(shape))
+    f.update(_overlap_figures(*blk.get(0, 'u8', 4)))
+    if cldice:
+        f.update(_read_cldice(blk, o_cl))
+    if topology:
+        (bp, cp), (bt, ct) = _read_topology(blk, o_top), _read_topology(blk, o_top + TOPOLOGY_BYTES)
+        f.update(betti_pred=bp, betti_truth=bt, euler_pred=cp, euler_truth=ct, betti_error=tuple(abs(a - b) for a, b in zip(bp, bt)),
+                 euler_error=abs(cp - ct))
+    if surface:
+        f.update(_read_surfaces_and_distances(blk, o_surf, s, percentile))
+    return SegmentationScores(**f)

@@ -1011,6 +1011,18 @@ class VanGan:
         mask = self.segment_mask(gen, raw, subvol_size, threshold=threshold, min_size=min_size, connectivity=connectivity, fill_holes=True, **kw)
         return postprocess.vessel_graph(mask, sampling, fill=False, min_spur=min_spur)
 
+    def evaluate_volume(self, gen: str, raw, truth, subvol_size=None, *, sampling=None, percentile=95.0, topology: bool = True, surface: bool = True,
+                        cldice: bool = True, max_passes=None, threshold=127.5, min_size=64, connectivity=3, fill_holes: bool = False, **kw):
+        """Raw volume and its ground truth (a uint8 / bool mask [X,Y,Z] on the device) -> (mask, scores): segment_mask(gen, raw,
+        subvol_size, ...) followed by postprocess.evaluate_segmentation(mask, truth, sampling, percentile, topology, surface, cldice,
+        max_passes) -- the SegmentationScores of the segmentation: overlap, clDice, Betti numbers, surface distances.  The arguments
+        of the scoring are checked before anything runs."""
+        from . import postprocess
+        postprocess._sampling(sampling), postprocess._percentile(percentile), postprocess._max_passes(max_passes)
+        postprocess._device_volume(truth, (torch.uint8, torch.bool), 'truth')
+        mask = self.segment_mask(gen, raw, subvol_size, threshold=threshold, min_size=min_size, connectivity=connectivity, fill_holes=fill_holes, **kw)
+        return mask, postprocess.evaluate_segmentation(mask, truth, sampling, percentile, topology, surface, cldice, max_passes)
+
     # ------------------------------------------------------------------------------------------------
     def save_checkpoint(self, epoch: int):
         """vangan.py:247-250 (own format: the TF tensor-bundle format is not readable without TF).  The replicas hold identical
