@@ -213,9 +213,21 @@ def fin_stress_cases() -> Dict[str, dict]:
 # ----------------------------------------------------------------------------------------------------------------------
 # InstanceNorm backward: random operands for a regime and its float64 reference (plain torch on the device)
 # ----------------------------------------------------------------------------------------------------------------------
-def anb_operands(r: dict, dev, seed=0):
+def anb_bytes(r: dict) -> int:
+    """Upper bound of the guarded-arena bytes of one regime's operands: g, x (+ x1) and dx on the padded grid at four bytes an element,
+    one more for slack, and 32 slots of up to 1 MiB for the per-(sample, channel) arrays."""
+    import guarded
+    cs = max(r['C'], r['dx_cstride'])
+    big = 4 * r['N'] * (r['D'] + 2) * (r['H'] + 2) * (r['W'] + 2) * cs
+    return 4 * guarded.slot_cost(big) + 32 * guarded.slot_cost(1 << 20)
+
+
+def anb_operands(r: dict, dev, seed=0, arena=None):
     """Random tensors for an InstanceNorm-backward regime (dict of its fields).  Samples >= alias_n0 read the forward tensors and
-    per-(sample, channel) constants of sample n - alias_shift: those have alias_n0 samples."""
+    per-(sample, channel) constants of sample n - alias_shift: those have alias_n0 samples.
+    arena (tests/guarded.py): every tensor a descriptor points at is a slot of it -- what the kernels only read sealed, a dx that is
+    overwritten 0xFF bytes, one that is accumulated into (or written in a channel slice) its random contents, sums and gamma / beta
+    gradients zeros.  t['dx0'] stays a plain copy."""
     g = torch.Generator(device=dev).manual_seed(seed)
     N, D, H, W, C = r['N'], r['D'], r['H'], r['W'], r['C']
     Nx = r['alias_n0'] if r['alias_n0'] > 0 else N
@@ -248,6 +260,17 @@ def anb_operands(r: dict, dev, seed=0):
         t['dgamma'], t['dbeta'] = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
     from van_gan_amd import ops
     t['red'] = torch.zeros(ops.STRIPES * N * C * 2 + 4, device=dev)
+    if arena is not None:
+        for k in ('g', 'x', 'x1', 'scale', 'shift', 'mean', 'rstd', 'gamma', 'mult'):
+            if k in t:
+                t[k] = arena.put(t[k], name=k)
+        if r['accumulate'] or cs != C:
+            t['dx'] = arena.put(t['dx'], name='dx', mutable=True)
+        else:
+            t['dx'] = arena.out(t['dx'].shape, dxdt, None, name='dx')
+        for k in ('dgamma', 'dbeta', 'red'):
+            if k in t:
+                t[k] = arena.out(t[k].shape, torch.float32, 0.0, name=k)
     return t
 
 
@@ -333,21 +356,24 @@ def anb_check(r: dict, t: dict, ref, name: str, stats: bool = True) -> dict:
     return err
 
 
-def run_anb(r: dict, dev, seed=0, name='') -> dict:
-    """Statistics (when norm) then apply, as the step runs them."""
+def run_anb(r: dict, dev, seed=0, name='', arena=None) -> dict:
+    """Statistics (when norm) then apply, as the step runs them.  arena: operands from it, verified after the parity assertions."""
     from van_gan_amd import ops
-    t = anb_operands(r, dev, seed)
+    t = anb_operands(r, dev, seed, arena)
     d = anb_desc(r, t)
     if r['norm']:
         ops.actnorm_stats(d)
     ops.actnorm_run(d, stats_done=True)
     torch.cuda.synchronize()
-    return anb_check(r, t, anb_reference(r, t), name)
+    err = anb_check(r, t, anb_reference(r, t), name)
+    if arena is not None:
+        arena.verify()
+    return err
 
 
-def run_apply2(r1: dict, r2: dict, dev, seed=0, name='') -> dict:
+def run_apply2(r1: dict, r2: dict, dev, seed=0, name='', arena=None) -> dict:
     from van_gan_amd import ops
-    t1, t2 = anb_operands(r1, dev, seed), anb_operands(r2, dev, seed + 1)
+    t1, t2 = anb_operands(r1, dev, seed, arena), anb_operands(r2, dev, seed + 1, arena)
     d1, d2 = anb_desc(r1, t1), anb_desc(r2, t2)
     for r, d in ((r1, d1), (r2, d2)):
         if r['norm']:
@@ -356,18 +382,21 @@ def run_apply2(r1: dict, r2: dict, dev, seed=0, name='') -> dict:
     torch.cuda.synchronize()
     e1 = anb_check(r1, t1, anb_reference(r1, t1), name + ' job 1')
     e2 = anb_check(r2, t2, anb_reference(r2, t2), name + ' job 2')
+    if arena is not None:
+        arena.verify()
     return {k + '1': v for k, v in e1.items()} | {k + '2': v for k, v in e2.items()}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # InstanceNorm finalisation tail
 # ----------------------------------------------------------------------------------------------------------------------
-def fin_build(recipe, N, cout, dev, seed=0):
-    """A FinDesc for the recorded jobs with random gamma / beta / mult and a zeroed ticket -> (FinDesc, job tensors)."""
+def fin_build(recipe, N, cout, dev, seed=0, arena=None):
+    """A FinDesc for the recorded jobs with random gamma / beta / mult and a zeroed ticket -> (FinDesc, job tensors).  arena: the ticket
+    word, gamma / beta / mult (sealed) and the four output arrays (0xFF bytes: NaN, as without it) are slots of it."""
     from van_gan_amd import _lib, ops
     g = torch.Generator(device=dev).manual_seed(seed)
     f = _lib.FinDesc()
-    tk = torch.zeros(4, dtype=torch.int32, device=dev)
+    tk = LR.dev_out(arena, (4,), torch.int32, dev, 0, 'ticket')
     f.ticket, f.count, f.eps, f.njobs = tk.data_ptr(), float(recipe['fin']['count']), ops.IN_EPS, len(recipe['fin']['jobs'])
     jobs = []
     for j, q in enumerate(recipe['fin']['jobs']):
@@ -375,8 +404,11 @@ def fin_build(recipe, N, cout, dev, seed=0):
         jt = dict(c_off=q['c_off'], c_tot=ct, gamma=torch.rand(ct, generator=g, device=dev) + 0.5 if q['gamma'] else None,
                   beta=torch.randn(ct, generator=g, device=dev) * 0.3 if q['beta'] else None,
                   mult=(torch.rand(N, ct, generator=g, device=dev) > 0.3).float() * 2.0 if q['mult'] else None)
+        for k in ('gamma', 'beta', 'mult'):
+            if arena is not None and jt[k] is not None:
+                jt[k] = arena.put(jt[k], name='job %d %s' % (j, k))
         for k in ('scale', 'shift', 'mean', 'rstd'):
-            jt[k] = torch.full((N, ct), float('nan'), device=dev)
+            jt[k] = LR.dev_out(arena, (N, ct), torch.float32, dev, float('nan'), 'job %d %s' % (j, k), must_write=True)
         fq = f.job[j]
         fq.gamma, fq.beta, fq.mult = [None if jt[k] is None else jt[k].data_ptr() for k in ('gamma', 'beta', 'mult')]
         fq.scale, fq.shift, fq.mean, fq.rstd = [jt[k].data_ptr() for k in ('scale', 'shift', 'mean', 'rstd')]
@@ -426,24 +458,24 @@ def fin_untouched(jobs, cout) -> bool:
     return ok
 
 
-def run_fin(recipe, expect_variant, dev, seed=5) -> float:
+def run_fin(recipe, expect_variant, dev, seed=5, arena=None) -> float:
     """The recorded forward call with its finalisation tail (random contents; the convolution itself is compared with the oracle by
     tests/test_gpu_layers.py): scale / shift / mean / rstd of every job against float64 statistics of the stored output."""
     L = recipe['layer']
     g = torch.Generator().manual_seed(seed)
-    st, lay = LR.make_layer_from(L, dev)
+    st, lay = LR.make_layer_from(L, dev, arena=arena)
     lay.pack()
     sr = recipe['src']
     N = sr['N']
-    src, _ = LR.make_operand(sr, L['pad'], dev, g)
+    src, _ = LR.make_operand(sr, L['pad'], dev, g, arena=arena)
     odt = torch.float32 if recipe['out_f32'] else torch.bfloat16
-    out = torch.zeros(N, *lay.out_dims, L['cout'], dtype=odt, device=dev)
-    sums = torch.zeros(8, N, L['cout'], 2, device=dev)
+    out = LR.dev_out(arena, (N,) + tuple(lay.out_dims) + (L['cout'],), odt, dev, 0.0, 'out', must_write=True)
+    sums = LR.dev_out(arena, (8, N, L['cout'], 2), torch.float32, dev, 0.0, 'out_sums')
     res = rs = rb = None
     if recipe['res']:
-        res = torch.randn(N, *lay.out_dims, L['cout'], generator=g).to(torch.bfloat16).to(dev)
-        rs, rb = (torch.rand(N, L['cout'], generator=g) + 0.5).to(dev), torch.randn(N, L['cout'], generator=g).to(dev)
-    f, _, jobs = fin_build(recipe, N, L['cout'], dev, seed)
+        res = LR.dev_in(arena, torch.randn(N, *lay.out_dims, L['cout'], generator=g).to(torch.bfloat16), dev, 'res')
+        rs, rb = LR.dev_in(arena, torch.rand(N, L['cout'], generator=g) + 0.5, dev, 'res_scale'), LR.dev_in(arena, torch.randn(N, L['cout'], generator=g), dev, 'res_shift')
+    f, _, jobs = fin_build(recipe, N, L['cout'], dev, seed, arena)
     call = lambda: lay.forward(src, out, sums=sums, res=res, res_scale=rs, res_shift=rb, tanh=recipe['tanh'], fin=f)
     assert LR.dry_variants(call) == [expect_variant]
     call()
@@ -452,30 +484,32 @@ def run_fin(recipe, expect_variant, dev, seed=5) -> float:
     err = float(fin_errors(jobs, mean, rstd, L['cout']))
     assert err <= 1e-4, 'finalisation tail rel %.2e' % err
     assert fin_untouched(jobs, L['cout'])
+    if arena is not None:
+        arena.verify()
     return err
 
 
-def stress_fin(recipe, expect_variant, dev, launches=200, seed=6) -> float:
+def stress_fin(recipe, expect_variant, dev, launches=200, seed=6, arena=None) -> float:
     """The tail under load: `launches` launches alternating between two streams, each with fresh (zeroed) sums and ticket; every
     launch's finalised statistics within the bound of run_fin.  A last workgroup that reads a stripe before every contribution has
     landed (or a ticket that does not count every workgroup) finalises from partial sums."""
     L = recipe['layer']
     g = torch.Generator().manual_seed(seed)
-    st, lay = LR.make_layer_from(L, dev)
+    st, lay = LR.make_layer_from(L, dev, arena=arena)
     lay.pack()
     sr = recipe['src']
     N = sr['N']
-    src, _ = LR.make_operand(sr, L['pad'], dev, g)
+    src, _ = LR.make_operand(sr, L['pad'], dev, g, arena=arena)
     odt = torch.float32 if recipe['out_f32'] else torch.bfloat16
     res = rs = rb = None
     if recipe['res']:
-        res = torch.randn(N, *lay.out_dims, L['cout'], generator=g).to(torch.bfloat16).to(dev)
-        rs, rb = (torch.rand(N, L['cout'], generator=g) + 0.5).to(dev), torch.randn(N, L['cout'], generator=g).to(dev)
+        res = LR.dev_in(arena, torch.randn(N, *lay.out_dims, L['cout'], generator=g).to(torch.bfloat16), dev, 'res')
+        rs, rb = LR.dev_in(arena, torch.rand(N, L['cout'], generator=g) + 0.5, dev, 'res_scale'), LR.dev_in(arena, torch.randn(N, L['cout'], generator=g), dev, 'res_shift')
     lanes = []
     for i in range(2):
-        out = torch.zeros(N, *lay.out_dims, L['cout'], dtype=odt, device=dev)
-        sums = torch.zeros(8, N, L['cout'], 2, device=dev)
-        f, tk, jobs = fin_build(recipe, N, L['cout'], dev, seed + i)
+        out = LR.dev_out(arena, (N,) + tuple(lay.out_dims) + (L['cout'],), odt, dev, 0.0, 'out %d' % i, must_write=True)
+        sums = LR.dev_out(arena, (8, N, L['cout'], 2), torch.float32, dev, 0.0, 'out_sums %d' % i)
+        f, tk, jobs = fin_build(recipe, N, L['cout'], dev, seed + i, arena)
         lanes.append((out, sums, f, tk, jobs))
     call = lambda ln: lay.forward(src, ln[0], sums=ln[1], res=res, res_scale=rs, res_shift=rb, tanh=recipe['tanh'], fin=ln[2])
     assert LR.dry_variants(lambda: call(lanes[0])) == [expect_variant]
@@ -498,4 +532,6 @@ def stress_fin(recipe, expect_variant, dev, launches=200, seed=6) -> float:
     torch.cuda.synchronize()
     w = max(float(x) for x in worst)
     assert w <= 1e-4, 'finalisation tail under load: worst rel %.2e over %d launches' % (w, launches)
+    if arena is not None:
+        arena.verify()               # once, after the loop: a check per launch would serialise the two streams
     return w

@@ -154,6 +154,16 @@ def inference_needed_variants():
 
 def recipe_variant(recipe) -> str:
     """The variant a recorded FORWARD call selects, by a CPU dry run of the rebuilt call (no contents: empty tensors)."""
+    got = dry_variants(empty_call(recipe))
+    assert len(got) == 1
+    return got[0]
+
+
+def empty_call(recipe):
+    """The call run_recipe rebuilds from `recipe`, on empty CPU tensors, as a function to issue inside ops.DryRun -- once per workspace
+    size when a test searches the size at which the plan changes (tests/containment_cases.py)."""
+    if recipe['kind'] != 'fwd':
+        return _empty_grad_call(recipe)
     from van_gan_amd.ops import Src
     assert recipe['kind'] == 'fwd'
     L, sr = recipe['layer'], recipe['src']
@@ -166,11 +176,9 @@ def recipe_variant(recipe) -> str:
               act=sr['act'], noise=e(N, *[n + 2 * sr['noise_pad'] for n in dims], c0 + c1) if sr['noise'] else None, noise_pad=sr['noise_pad'])
     out = e(N, *lay.out_dims, L['cout'], dt=torch.float32 if recipe['out_f32'] else torch.bfloat16)
     pc = lambda: e(N, L['cout'], dt=torch.float32)
-    got = dry_variants(lambda: lay.forward(src, out, sums=e(8, N, L['cout'], 2, dt=torch.float32) if recipe['sums'] else None,
-                                           res=e(N, *lay.out_dims, L['cout']) if recipe['res'] else None,
-                                           res_scale=pc() if recipe['res'] else None, res_shift=pc() if recipe['res'] else None, tanh=recipe['tanh']))
-    assert len(got) == 1
-    return got[0]
+    sums, res = e(8, N, L['cout'], 2, dt=torch.float32) if recipe['sums'] else None, e(N, *lay.out_dims, L['cout']) if recipe['res'] else None
+    rs, rb = (pc(), pc()) if recipe['res'] else (None, None)
+    return lambda: lay.forward(src, out, sums=sums, res=res, res_scale=rs, res_shift=rb, tanh=recipe['tanh'])
 
 
 SHRINK_ABOVE = 1e9          # MACs: cheaper calls are replayed as recorded (a shrunk grid has fewer tiles and fewer workgroups)
@@ -377,10 +385,16 @@ def batch3_only_variants():
 def replay_variant(recipe) -> str:
     """recipe_variant for all three kinds: the variant the call that run_recipe rebuilds from `recipe` selects, by a CPU dry run on empty
     tensors (a data gradient may be issued in several launches of one variant: the set must have one element)."""
+    if recipe['kind'] == 'fwd':
+        return recipe_variant(recipe)
+    got = dry_variants(empty_call(recipe))
+    assert len(set(got)) == 1, got
+    return got[0]
+
+
+def _empty_grad_call(recipe):
     from van_gan_amd import ops
     kind, L = recipe['kind'], recipe['layer']
-    if kind == 'fwd':
-        return recipe_variant(recipe)
     _, lay = make_layer_from(L, 'cpu')
     e = lambda *shp, dt=torch.bfloat16: torch.empty(*shp, dtype=dt)
     if kind == 'wgrad':
@@ -391,7 +405,7 @@ def replay_variant(recipe) -> str:
                       scale=e(N, c0 + c1, dt=torch.float32) if sr['affine'] else None, shift=e(N, c0 + c1, dt=torch.float32) if sr['affine'] else None,
                       act=sr['act'], noise=e(N, *[n + 2 * sr['noise_pad'] for n in dims], c0 + c1) if sr['noise'] else None, noise_pad=sr['noise_pad'])
         dy = e(N, *lay.out_dims, L['cout'], dt=torch.float32 if recipe['dy_f32'] else torch.bfloat16)
-        got = dry_variants(lambda: lay.wgrad(src, dy))
+        return lambda: lay.wgrad(src, dy)
     else:
         N, Cc = recipe['N'], L['cin']
         dy = e(N, *lay.out_dims, L['cout'], dt=torch.float32 if recipe['dy_f32'] else torch.bfloat16)
@@ -405,9 +419,7 @@ def replay_variant(recipe) -> str:
                                      shift=f(N, Cc), act=bs['act'], norm=True, gamma=f(Cc), mean=f(N, Cc), rstd=f(N, Cc),
                                      red=f(ops.STRIPES * N * Cc * 2 + 4), accumulate=False, x1=e(N, *dims_in, Cc - c0) if bs['cat'] else None,
                                      c_x0=c0 if bs['cat'] else 0, x0_shift=sh, dgamma=f(Cc), dbeta=f(Cc))
-        got = dry_variants(lambda: lay.dgrad(dy, N, dp, accumulate=recipe['accumulate'], bstat=bdesc))
-    assert len(set(got)) == 1, got
-    return got[0]
+        return lambda: lay.dgrad(dy, N, dp, accumulate=recipe['accumulate'], bstat=bdesc)
 
 
 def out_grid(recipe) -> Tuple[int, int, int]:
@@ -432,16 +444,61 @@ def _ref_dtype(macs):
     return torch.float64 if macs < 3e9 else torch.float32      # float32 CPU accumulation error (~1e-6) << one bf16 rounding
 
 
-def make_layer_from(ctor, dev, seed=0, dtype=torch.bfloat16):
+# ---- where the replays' device tensors come from: plain torch allocations, or slots of a guarded arena (tests/guarded.py) ----
+def dev_in(arena, host, dev, name=None, mutable=False):
+    """An input operand on the device: a copy of `host` (None stays None); with an arena, a sealed slot of it (mutable: an operand the
+    call accumulates into, not sealed)."""
+    if host is None:
+        return None
+    return host.to(dev) if arena is None else arena.put(host, name=name, mutable=mutable)
+
+
+def dev_out(arena, shape, dtype, dev, fill, name=None, must_write=False):
+    """An output on the device, every element `fill`.  must_write, with an arena: the call has to store every element, so the slot starts
+    as 0xFF bytes (a NaN in every float format) instead, and one it skips fails parity whatever the reference holds there."""
+    if arena is None:
+        return torch.full(tuple(shape), fill, dtype=dtype, device=dev)
+    return arena.out(shape, dtype, None if must_write else fill, name=name)
+
+
+def recipe_bytes(recipe) -> int:
+    """Upper bound of the guarded-arena bytes a replay of `recipe` takes (run_recipe, run_fin, the stress loops).  On the layer's
+    reflect-padded input grid: the source or the data gradient (at most 4 bytes an element), the noise or the statistics' forward
+    tensors and their dx (2 + 2) -- 8 bytes, budgeted 12; on its output grid: the output or dY (4) and the residual (2), three outputs
+    in a stress loop (2 each) -- 6 bytes, budgeted 12; the weight and gradient tables; 64 slots of up to 1 MiB for everything small."""
+    import guarded
+    L = recipe['layer']
+    N = recipe_n(recipe)
+    s, k = L['stride'], L['k']
+    vin = math.prod(n + 2 for n in L['in_dims'])
+    vout = math.prod((n + 2 - k) // s + 1 if L['pad'] == 'reflect' else -(-n // s) for n in L['in_dims'])
+    big = [4 * N * vin * L['cin']] * 3 + [4 * N * vout * L['cout']] * 3 + [4 * k ** 3 * L['cin'] * L['cout'] + 4 * L['cout']] * 2
+    return sum(guarded.slot_cost(b) for b in big) + 64 * guarded.slot_cost(1 << 20)
+
+
+def guarded_for(recipe, dev):
+    """A guarded arena big enough for one replay of `recipe`."""
+    import guarded
+    return guarded.GuardedArena(recipe_bytes(recipe), dev)
+
+
+def make_layer_from(ctor, dev, seed=0, dtype=torch.bfloat16, arena=None):
+    """arena: the parameter and gradient tables of the layer's store are slots of it (the weights sealed once they are set).  The packed
+    operands stay what ConvLayer allocates: the pack kernels' outputs, read-only for every launch of these replays."""
     from van_gan_amd.nets import ParamStore
     from van_gan_amd.ops import ConvLayer
     k, cin, cout = ctor['k'], ctor['cin'], ctor['cout']
     specs = [('c.w', (k, k, k, cin, cout), 'x')] + ([('c.b', (cout,), 'x')] if ctor['bias'] else [])
     st = ParamStore(specs, dev)
+    if arena is not None:               # before ConvLayer takes its views
+        st.w = arena.out((st.total,), torch.float32, 0.0, name='weights')
+        st.g = arena.out((st.total,), torch.float32, 0.0, name='weight gradients')
     g = torch.Generator().manual_seed(seed)
     st.param('c.w').copy_(torch.randn(k, k, k, cin, cout, generator=g) / math.sqrt(k ** 3 * cin))
     if ctor['bias']:
         st.param('c.b').copy_(torch.randn(cout, generator=g) * 0.1)
+    if arena is not None:
+        arena.seal(st.w)
     lay = ConvLayer(st, 'c', k, cin, cout, ctor['stride'], ctor['pad'], ctor['bias'], ctor['in_dims'],
                     need_dgrad=ctor['need_dgrad'], dtype=dtype)
     if ctor.get('c_up'):
@@ -449,8 +506,9 @@ def make_layer_from(ctor, dev, seed=0, dtype=torch.bfloat16):
     return st, lay
 
 
-def make_operand(sr, pad, dev, g, storage=torch.bfloat16):
-    """Random contents for a Src recipe -> (Src on dev, host tensors).  storage: the 16-bit type of the stored tensors."""
+def make_operand(sr, pad, dev, g, storage=torch.bfloat16, arena=None):
+    """Random contents for a Src recipe -> (Src on dev, host tensors).  storage: the 16-bit type of the stored tensors.  arena: every
+    device tensor of the Src is a sealed slot of it."""
     from van_gan_amd.ops import Src
     N, dims, c0, c1, sh = sr['N'], tuple(sr['dims']), sr['c0'], sr['c1'], sr['shift0']
     C_ = c0 + c1
@@ -464,9 +522,9 @@ def make_operand(sr, pad, dev, g, storage=torch.bfloat16):
     if sr['noise']:
         npd = sr['noise_pad']
         noise = (torch.randn(N, *[n + 2 * npd for n in dims], C_, generator=g) * 0.1).to(storage)
-    d = lambda t: None if t is None else t.to(dev)
-    src = Src(d(x0), (N,) + dims, c0, d(x1), c1, shift0=sh, f32=sr['f32'], scale=d(scale), shift=d(shift), act=sr['act'],
-              noise=d(noise), noise_pad=sr['noise_pad'])
+    d = lambda t, name: dev_in(arena, t, dev, name)
+    src = Src(d(x0, 'src0'), (N,) + dims, c0, d(x1, 'src1'), c1, shift0=sh, f32=sr['f32'], scale=d(scale, 'in_scale'), shift=d(shift, 'in_shift'),
+              act=sr['act'], noise=d(noise, 'noise'), noise_pad=sr['noise_pad'])
     return src, dict(x0=x0, x1=x1, scale=scale, shift=shift, noise=noise)
 
 
@@ -533,13 +591,18 @@ FWD_TOL = {torch.bfloat16: dict(rel=1.2e-2, floor=2e-3, sums=2e-2, f32=1e-4),
            torch.float16: dict(rel=1.5e-3, floor=2.5e-4, sums=2.5e-3, f32=1e-4)}
 
 
-def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=torch.bfloat16):
+def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=torch.bfloat16, arena=None, after_launch=None):
     """Replay one recorded call on `dev` with random contents and compare with the oracle.  Tolerances as in
     tests/test_gpu_ops.py: identical bf16-rounded operands into the reference, so only fp32 accumulation order and the one
     rounding of the stored output differ.
     storage=torch.float16 (forward calls only, made inside ops.Fp16()): 16-bit tensors are IEEE half, the reference rounds with
     .half() where it rounds to bf16 otherwise, bounds FWD_TOL[torch.float16]; a single-channel fp32 residual (res_c1, stem.cb) is
-    replayed as recorded.  Returns the measured errors of the replay."""
+    replayed as recorded.  Returns the measured errors of the replay.
+    arena (tests/guarded.py): every device operand is a sealed slot of it and every output a slot that starts as 0xFF bytes (accumulators
+    as zeros); after the parity assertions, which are the same either way, arena.verify(): every guard intact, every input unchanged.
+    after_launch(call, result, reset): called once the launch has run and before anything is compared -- `result` the tensor the call
+    writes, reset() puts what the call accumulates into back to its state before the launch, call() launches again (the parity
+    assertions then see the last launch; tests/test_gpu_containment.py relaunches into a workspace it has not touched)."""
     from oracle import vangan_oracle as O
     L = recipe['layer']
     kind, pad, stride = recipe['kind'], L['pad'], L['stride']
@@ -547,7 +610,7 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
     g = torch.Generator().manual_seed(seed)
     half = storage != torch.bfloat16
     assert storage in FWD_TOL and (not half or kind == 'fwd')
-    st, lay = make_layer_from(L, dev, dtype=storage)
+    st, lay = make_layer_from(L, dev, dtype=storage, arena=arena)
     lay.pack()
     w_ref = bf(st.param('c.w').cpu().to(dt), storage)
     b_ref = st.param('c.b').cpu().to(dt) if L['bias'] else None
@@ -555,24 +618,26 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
     if kind in ('fwd', 'wgrad'):
         sr = recipe['src']
         N = sr['N']
-        src, host = make_operand(sr, pad, dev, g, storage)
+        src, host = make_operand(sr, pad, dev, g, storage, arena)
         ap = ref_operand(sr, host, pad, dt, storage)
     if kind == 'fwd':
         tol = FWD_TOL[storage]
         odt = torch.float32 if recipe['out_f32'] else storage
-        out = torch.zeros(N, *lay.out_dims, L['cout'], dtype=odt, device=dev)
-        sums = torch.zeros(8, N, L['cout'], 2, device=dev) if recipe['sums'] else None
+        out = dev_out(arena, (N,) + tuple(lay.out_dims) + (L['cout'],), odt, dev, 0.0, 'out', must_write=True)
+        sums = dev_out(arena, (8, N, L['cout'], 2), torch.float32, dev, 0.0, 'out_sums') if recipe['sums'] else None
         res = rs = rb = None
         c1 = half and bool(recipe.get('res_c1'))
         if recipe['res']:
             res = torch.randn(N, *lay.out_dims, 1, generator=g) if c1 else torch.randn(N, *lay.out_dims, L['cout'], generator=g).to(storage)
             rs, rb = torch.rand(N, L['cout'], generator=g) + 0.5, torch.randn(N, L['cout'], generator=g)
-        call = lambda: lay.forward(src, out, sums=sums, res=None if res is None else res.to(dev),
-                                   res_scale=None if rs is None else rs.to(dev), res_shift=None if rb is None else rb.to(dev),
+        res_d, rs_d, rb_d = dev_in(arena, res, dev, 'res'), dev_in(arena, rs, dev, 'res_scale'), dev_in(arena, rb, dev, 'res_shift')
+        call = lambda: lay.forward(src, out, sums=sums, res=res_d, res_scale=rs_d, res_shift=rb_d,
                                    tanh=recipe['tanh'], **(dict(res_c1=True) if c1 else {}))
         assert dry_variants(call) == [expect_variant]
         call()
         torch.cuda.synchronize()
+        if after_launch is not None:
+            after_launch(call, out, lambda: None if sums is None else sums.zero_())
         y = O.to_ndhwc(O.conv3d(ap, w_ref, b_ref, stride, conv_pad))
         if res is not None:
             y = y + res.to(dt) * rs.to(dt).view(N, 1, 1, 1, -1) + rb.to(dt).view(N, 1, 1, 1, -1)
@@ -590,17 +655,22 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
             ref_sums = torch.stack([yq.sum(dim=(1, 2, 3)), (yq ** 2).sum(dim=(1, 2, 3))], dim=-1)
             err['sums'] = rel_l2(sums.sum(0), ref_sums)
             assert err['sums'] < tol['sums'], 'IN statistics rel %.2e' % err['sums']
+        if arena is not None:
+            arena.verify()
         return err
     odims = lay.out_dims
     dy = torch.randn(recipe['src']['N'] if kind == 'wgrad' else recipe['N'], *odims, L['cout'], generator=g)
     dys = dy if recipe['dy_f32'] else dy.to(torch.bfloat16)
     dy_ref = O.to_ncdhw(bf(dys.to(dt)))                 # the kernels round dY to bf16 when they stage it
+    dy_d = dev_in(arena, dys, dev, 'dy')
     if kind == 'wgrad':
-        call = lambda: lay.wgrad(src, dys.to(dev))
+        call = lambda: lay.wgrad(src, dy_d)
         assert dry_variants(call) == [expect_variant]
         st.g.zero_()
         call()
         torch.cuda.synchronize()
+        if after_launch is not None:
+            after_launch(call, st.g, lambda: st.g.zero_())
         w = w_ref.clone().requires_grad_(True)
         (O.conv3d(ap, w, None, stride, conv_pad) * dy_ref).sum().backward()
         err = dict(w=rel_l2(st.grad('c.w'), w.grad))
@@ -608,6 +678,8 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
         if L['bias']:
             err['b'] = rel_l2(st.grad('c.b'), dy_ref.sum(dim=(0, 2, 3, 4)))
             assert err['b'] < 2e-3, 'bias gradient rel %.2e' % err['b']
+        if arena is not None:
+            arena.verify()
         return err
     # data gradient: on the reflect-PADDED grid for 'reflect' convs (the fold is a separate kernel), plain grid for 'same'
     N = recipe['N']
@@ -615,9 +687,9 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
     prior = None
     if recipe['accumulate']:
         prior = torch.randn(N, *lay.buf_dims, L['cin'], generator=g).to(odt)
-        dp = prior.to(dev).clone()
+        dp = prior.to(dev).clone() if arena is None else arena.put(prior, name='dx (accumulated into)', mutable=True)
     else:
-        dp = torch.full((N,) + tuple(lay.buf_dims) + (L['cin'],), 7.0, dtype=odt, device=dev)       # must be overwritten everywhere
+        dp = dev_out(arena, (N,) + tuple(lay.buf_dims) + (L['cin'],), odt, dev, 7.0, 'dx', must_write=True)   # must be overwritten everywhere
     bs = recipe.get('bstat')
     bdesc = None
     if bs:
@@ -630,19 +702,21 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
         bx1 = torch.randn(N, *dims_in, Cc - c0, generator=g).to(torch.bfloat16) if bs['cat'] else None
         bsc, bsf = torch.rand(N, Cc, generator=g) + 0.5, torch.randn(N, Cc, generator=g) * 0.3
         bmu, brs = torch.randn(N, Cc, generator=g) * 0.2, torch.rand(N, Cc, generator=g) + 0.5
-        red = torch.zeros(ops.STRIPES * N * Cc * 2 + 4, device=dev)
-        dgam, dbet = torch.zeros(Cc, device=dev), torch.zeros(Cc, device=dev)
-        dxo = torch.zeros(N, *dims_in, Cc, dtype=torch.bfloat16, device=dev)
-        tod = lambda t: None if t is None else t.to(dev)
-        bdesc = ops.actnorm_desc(dp, bs['pad'], tod(bx0), (N,) + dims_in, Cc, dxo, scale=tod(bsc), shift=tod(bsf), act=bs['act'], norm=True,
-                                 gamma=torch.ones(Cc, device=dev), mean=tod(bmu), rstd=tod(brs), red=red, accumulate=False, x1=tod(bx1),
+        red = dev_out(arena, (ops.STRIPES * N * Cc * 2 + 4,), torch.float32, dev, 0.0, 'red')
+        dgam, dbet = dev_out(arena, (Cc,), torch.float32, dev, 0.0, 'dgamma'), dev_out(arena, (Cc,), torch.float32, dev, 0.0, 'dbeta')
+        dxo = dev_out(arena, (N,) + dims_in + (Cc,), torch.bfloat16, dev, 0.0, 'IN-backward dx', must_write=True)
+        tod = lambda t, name: dev_in(arena, t, dev, 'IN-backward ' + name)
+        bdesc = ops.actnorm_desc(dp, bs['pad'], tod(bx0, 'x0'), (N,) + dims_in, Cc, dxo, scale=tod(bsc, 'scale'), shift=tod(bsf, 'shift'), act=bs['act'], norm=True,
+                                 gamma=tod(torch.ones(Cc), 'gamma'), mean=tod(bmu, 'mean'), rstd=tod(brs, 'rstd'), red=red, accumulate=False, x1=tod(bx1, 'x1'),
                                  c_x0=c0 if bs['cat'] else 0, x0_shift=sh, dgamma=dgam, dbeta=dbet)
     done = []
-    call = lambda: done.append(lay.dgrad(dys.to(dev), N, dp, accumulate=recipe['accumulate'], bstat=bdesc))
+    call = lambda: done.append(lay.dgrad(dy_d, N, dp, accumulate=recipe['accumulate'], bstat=bdesc))
     got_variants = dry_variants(call)
     assert expect_variant in got_variants and len(set(got_variants)) == 1, (got_variants, expect_variant)
     call()
     torch.cuda.synchronize()
+    if after_launch is not None:
+        after_launch(call, dp, lambda: (None if prior is None else dp.copy_(prior), None if not bs else red.zero_()))
     if bs:
         assert done[-1] is True
         # reference statistics from the data gradient the kernel stored: transpose of the reflection pad, dn = g * act'(pre)
@@ -672,33 +746,37 @@ def run_recipe(recipe, expect_variant, dev, seed=1, precision='bf16', storage=to
     if prior is not None:
         ref = ref + prior.to(dt)
     close_bf16(dp, ref, 'data gradient', rel=2.5e-2, floor=6e-3)
+    if arena is not None:
+        arena.verify()
     return dict(dx=float((dp.double().cpu() - ref.double()).abs().max() / ref.double().abs().max()))
 
 
-def stress_recipe(recipe, expect_variant, dev, launches=200, seed=3):
+def stress_recipe(recipe, expect_variant, dev, launches=200, seed=3, arena=None):
     """K-split exchange under load: the recorded call `launches` times back to back, alternating between two streams (each with its
     own output buffer; the library's per-stream scratch -- partial tiles + arrival counters -- is reused by every launch of a
     stream), every output compared BITWISE with the first launch's.  The slices' partial tiles are added in slice order, so any
-    difference is a partial tile read before it was complete, or a counter that did not return to zero."""
+    difference is a partial tile read before it was complete, or a counter that did not return to zero.
+    arena (tests/guarded.py): operands and the three outputs are slots of it; guards and inputs are verified ONCE, after the loop (a
+    check per launch would put a host sync between the launches the loop is there to overlap)."""
     L = recipe['layer']
     kind = recipe['kind']
     g = torch.Generator().manual_seed(seed)
-    st, lay = make_layer_from(L, dev)
+    st, lay = make_layer_from(L, dev, arena=arena)
     lay.pack()
     streams = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
     if kind == 'fwd':
         sr = recipe['src']
-        src, _ = make_operand(sr, L['pad'], dev, g)
+        src, _ = make_operand(sr, L['pad'], dev, g, arena=arena)
         odt = torch.float32 if recipe['out_f32'] else torch.bfloat16
-        outs = [torch.zeros(sr['N'], *lay.out_dims, L['cout'], dtype=odt, device=dev) for _ in range(3)]
+        outs = [dev_out(arena, (sr['N'],) + tuple(lay.out_dims) + (L['cout'],), odt, dev, 0.0, 'out %d' % i, must_write=True) for i in range(3)]
         call = lambda o: lay.forward(src, o, tanh=recipe['tanh'])
     else:
         assert kind == 'dgrad' and not recipe['accumulate'] and not recipe.get('bstat')
         N = recipe['N']
         dy = torch.randn(N, *lay.out_dims, L['cout'], generator=g)
-        dys = (dy if recipe['dy_f32'] else dy.to(torch.bfloat16)).to(dev)
+        dys = dev_in(arena, dy if recipe['dy_f32'] else dy.to(torch.bfloat16), dev, 'dy')
         odt = torch.float32 if recipe['out_f32'] else torch.bfloat16
-        outs = [torch.zeros((N,) + tuple(lay.buf_dims) + (L['cin'],), dtype=odt, device=dev) for _ in range(3)]
+        outs = [dev_out(arena, (N,) + tuple(lay.buf_dims) + (L['cin'],), odt, dev, 0.0, 'dx %d' % i, must_write=True) for i in range(3)]
         call = lambda o: lay.dgrad(dys, N, o, accumulate=False)
     got = dry_variants(lambda: call(outs[2]))
     assert got == [expect_variant], (got, expect_variant)
@@ -717,3 +795,5 @@ def stress_recipe(recipe, expect_variant, dev, launches=200, seed=3):
     torch.cuda.synchronize()
     bad = int(bad)
     assert bad == 0, '%d elements differ from the first launch over %d launches on two streams' % (bad, launches)
+    if arena is not None:
+        arena.verify()

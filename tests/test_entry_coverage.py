@@ -73,12 +73,10 @@ UNTESTED_ON_PURPOSE = {
     'vg_conv3d_thin_np': ('host', 'channel padding the thin-layer specialist would use', None),
     'vg_conv3d_wgrad_variant': ('host', 'dry run of the weight-gradient dispatch (tests/test_variant_coverage.py reads it)', None),
     'vg_conv3d_dma_bn': ('host', 'column-block width of the LDS-DMA kernels for a descriptor', None),
-    'vg_conv3d_scratch_bytes': ('host', 'scratch size query', None),
     'vg_packed_ktot': ('host', 'packed-operand geometry', None),
     'vg_packed_rows': ('host', 'packed-operand geometry', None),
     'vg_value_mode_scratch_bytes': ('host', 'scratch size query', None),
     'vg_spectral_norm_blocks': ('host', 'workgroups per item of a spectral-norm table', None),
-    'vg_spectral_norm_scratch_bytes': ('host', 'scratch size query', None),
     'vg_in_param_grads': ('unreached', 'superseded by the ticketed tail of vg_actnorm_bwd_stats; kept in the ABI, no caller in the package', None),
     'vg_memset_zero': ('runtime', 'hipMemsetAsync under the library\'s stream handle, issued only by a recorded step (ops.zero_fill)', _REPLAY),
     'vg_copy_bytes': ('runtime', 'hipMemcpyAsync under the library\'s stream handle, issued only by a recorded step (ops.copy)', _REPLAY),

@@ -3,7 +3,9 @@ launch, stem shortcut and tanh call that BASELINE configs 2, 3 and 4 make, one p
 (tests/call_recipes.py; tests/test_call_coverage.py proves the list complete), the finalisation tail under load, the loss chain at the
 configs' (B, dims), Adam over the real parameter tables -- each against a float64 restatement on the same rounded operands, computed
 with plain torch on the device (the host where the device has no float64 kernel).  Tolerances of tests/test_gpu_ops.py: close_bf16 for
-bf16 outputs, relative L2 <= 1e-4 for fp32 outputs, relative error <= 1e-4 for scalar sums, unless stated otherwise."""
+bf16 outputs, relative L2 <= 1e-4 for fp32 outputs, relative error <= 1e-4 for scalar sums, unless stated otherwise.
+The recorded calls, the tails under load, the InstanceNorm-backward edges, the loss chain, the skeleton and Adam run inside a guarded
+arena (tests/guarded.py): after their parity assertions every guard byte is intact and every input unchanged."""
 import math
 
 import pytest
@@ -11,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import call_recipes as CR
+import guarded
 import layer_recipes as LR
 
 pytestmark = pytest.mark.gpu
@@ -34,9 +37,19 @@ def _sum_err(got, want):
 # ----------------------------------------------------------------------------------------------------------------------
 # the recorded calls
 # ----------------------------------------------------------------------------------------------------------------------
-def _decoder(blk, dev):
+def _decoder_bytes(blk) -> int:
+    """Guarded-arena bytes of _decoder: the concat-wide tensors (the padded gradient, two concat gradients) and, no wider together, dY,
+    the sources and their gradients -- budgeted as eight bf16 tensors on the padded grid with all channels -- and 32 small slots."""
+    N, (D, H, W) = blk['N'], blk['dims']
+    big = 2 * N * (D + 2) * (H + 2) * (W + 2) * (blk['c_low'] + blk['c_skip'])
+    return 8 * guarded.slot_cost(big) + 32 * guarded.slot_cost(1 << 20)
+
+
+def _decoder(blk, dev, arena=None):
     """vg_shortcut_dgrad_concat_norm (served where the split kernel has the shape, else the step's fall-back), vg_shortcut_dgrad_concat and vg_concat_bwd with every accumulate combination, at the
-    block's true shape, against float64 (the formulas of tests/test_gpu_ops.py's small-shape cases)."""
+    block's true shape, against float64 (the formulas of tests/test_gpu_ops.py's small-shape cases).
+    arena (tests/guarded.py): every tensor a launch reads is a sealed slot of it; dlow / dskip / the concat gradient the fall-back adds
+    into are one slot each, reloaded for every launch; verified after each group of launches."""
     from oracle import vangan_oracle as O
     from van_gan_amd import ops
     from van_gan_amd.nets import ParamStore
@@ -49,31 +62,39 @@ def _decoder(blk, dev):
     ru = lambda *s: torch.rand(*s, generator=g, device=dev)
     b16 = lambda t: t.to(torch.bfloat16)
     st = ParamStore([('c.w', (1, 1, 1, C_, cout), 'x'), ('c.b', (cout,), 'x')], dev)
+    if arena is not None:               # before ConvLayer takes its views
+        st.w = arena.out((st.total,), torch.float32, 0.0, name='weights')
+        st.g = arena.out((st.total,), torch.float32, 0.0, name='weight gradients')
     st.param('c.w').copy_(rn(1, 1, 1, C_, cout) / math.sqrt(C_))
     lay = ConvLayer(st, 'c', 1, C_, cout, 1, 'same', True, blk['dims'])
     lay.pack()
+    put = lambda t, name: t if arena is None else arena.put(t, name=name)
+    fresh = lambda t0, name: t0.clone() if arena is None else arena.put(t0, name=name, mutable=True)      # an in/out operand
+    reload = lambda t, t0: t0.clone() if arena is None else t.copy_(t0)
+    if arena is not None:
+        arena.seal(st.w)
     wT = st.param('c.w').to(torch.bfloat16).double().view(C_, cout).t()
-    dy = b16(rn(N, D, H, W, cout))
-    dp1 = b16(rn(N, D + 2, H + 2, W + 2, C_))
-    low, skip = b16(rn(N, D // 2, H // 2, W // 2, cl)), b16(rn(N, D, H, W, cs))
-    gamma, beta = ru(C_) + 0.5, rn(C_) * 0.2
-    mean, rstd = rn(N, C_) * 0.3, ru(N, C_) + 0.5
-    scale = gamma.view(1, C_) * rstd
-    shift = beta.view(1, C_) - mean * scale
+    dy = put(b16(rn(N, D, H, W, cout)), 'dy')
+    dp1 = put(b16(rn(N, D + 2, H + 2, W + 2, C_)), 'padded gradient')
+    low, skip = put(b16(rn(N, D // 2, H // 2, W // 2, cl)), 'low'), put(b16(rn(N, D, H, W, cs)), 'skip')
+    gamma, beta = put(ru(C_) + 0.5, 'gamma'), rn(C_) * 0.2
+    mean, rstd = put(rn(N, C_) * 0.3, 'mean'), put(ru(N, C_) + 0.5, 'rstd')
+    scale = put(gamma.view(1, C_) * rstd, 'scale')
+    shift = put(beta.view(1, C_) - mean * scale, 'shift')
     dlow0, dskip0 = b16(rn(N, D // 2, H // 2, W // 2, cl)), b16(rn(N, D, H, W, cs))
     pool = lambda t: t.view(N, D // 2, 2, H // 2, 2, W // 2, 2, -1).sum(dim=(2, 4, 6))
     err = {}
     # 1. the fused launch with the IN backward folded in (as the step runs it: statistics first)
-    dgamma, dbeta = torch.zeros(C_, device=dev), torch.zeros(C_, device=dev)
-    red = torch.zeros(ops.STRIPES * N * C_ * 2 + 4, device=dev)
-    dlow, dskip = dlow0.clone(), dskip0.clone()
+    dgamma, dbeta = LR.dev_out(arena, (C_,), torch.float32, dev, 0.0, 'dgamma'), LR.dev_out(arena, (C_,), torch.float32, dev, 0.0, 'dbeta')
+    red = LR.dev_out(arena, (ops.STRIPES * N * C_ * 2 + 4,), torch.float32, dev, 0.0, 'red')
+    dlow, dskip = fresh(dlow0, 'dlow'), fresh(dskip0, 'dskip')
     nd = ops.actnorm_desc(dp1, True, low, (N, D, H, W), C_, None, scale=scale, shift=shift, act=ops.ACT_RELU, norm=True, gamma=gamma,
                           mean=mean, rstd=rstd, red=red, accumulate=False, x1=skip, c_x0=cl, x0_shift=1, dgamma=dgamma, dbeta=dbeta)
     ops.actnorm_stats(nd)
     served = lay.dgrad_concat_norm(dy, N, nd, cl, dlow, dskip, acc_low=True, acc_skip=False)
     assert served == blk['served'], 'vg_shortcut_dgrad_concat_norm served: %s' % served
     if not served:              # the step's fall-back: apply pass into a concat-gradient buffer, then the shortcut's data gradient + split
-        dcat = torch.full((N, D, H, W, C_), 7.0, dtype=torch.bfloat16, device=dev)
+        dcat = LR.dev_out(arena, (N, D, H, W, C_), torch.bfloat16, dev, 7.0, 'concat gradient (fall-back)', must_write=True)
         ops.actnorm_set_dx(nd, dcat)
         ops.actnorm_run(nd, stats_done=True)
         lay.dgrad_concat(dy, N, dcat, cl, dlow, dskip, acc_low=True, acc_skip=False)
@@ -94,30 +115,36 @@ def _decoder(blk, dev):
     LR.close_bf16(dskip, full[..., cl:], 'norm-fused dskip')
     err['norm_dgamma'], err['norm_dbeta'] = LR.rel_l2(dgamma, r1.sum(0).flatten()), LR.rel_l2(dbeta, r0.sum(0).flatten())
     assert err['norm_dgamma'] <= 1e-4 and err['norm_dbeta'] <= 1e-4, err
+    if arena is not None:
+        arena.verify()
     del x, z, gf, dn, xh, dx, full
     # 2. the fused shortcut data gradient + concat backward (the fall-back of 1): dcat is only read
-    dcat = b16(rn(N, D, H, W, C_))
-    dcat0 = dcat.clone()
+    dcat0 = b16(rn(N, D, H, W, C_))
+    dcat = fresh(dcat0, 'concat gradient')
     full = dcat.double() + dy.double() @ wT
     for acc_low, acc_skip in ((False, False), (True, True)):
-        dlow, dskip, dcat = dlow0.clone(), dskip0.clone(), dcat0.clone()
+        dlow, dskip, dcat = reload(dlow, dlow0), reload(dskip, dskip0), reload(dcat, dcat0)
         lay.dgrad_concat(dy, N, dcat, cl, dlow, dskip, acc_low=acc_low, acc_skip=acc_skip)
         torch.cuda.synchronize()
         assert torch.equal(dcat, dcat0) == blk['served'], 'the fused launch only reads the concat gradient; the fall-back adds into it'
         LR.close_bf16(dlow, pool(full[..., :cl]) + (dlow0.double() if acc_low else 0), 'concat-fused dlow')
         LR.close_bf16(dskip, full[..., cl:] + (dskip0.double() if acc_skip else 0), 'concat-fused dskip')
+    if arena is not None:
+        arena.verify()
     # 3. vg_concat_bwd on its own, every accumulate combination
-    dcat = dcat0
+    dcat = dcat0 if arena is None else arena.seal(reload(dcat, dcat0))           # only read from here on
     for acc in range(4):
-        dlow, dskip = dlow0.clone(), dskip0.clone()
+        dlow, dskip = reload(dlow, dlow0), reload(dskip, dskip0)
         ops.concat_bwd(dcat, (N, D, H, W), cl, cs, dlow, dskip, acc_low=bool(acc & 1), acc_skip=bool(acc & 2))
         torch.cuda.synchronize()
         LR.close_bf16(dlow, pool(dcat.double()[..., :cl]) + (dlow0.double() if acc & 1 else 0), 'concat_bwd dlow')
         LR.close_bf16(dskip, dcat.double()[..., cl:] + (dskip0.double() if acc & 2 else 0), 'concat_bwd dskip')
+    if arena is not None:
+        arena.verify()
     return err
 
 
-def _stem_fwd(N, S, C_, dev, x=None, seed=21):
+def _stem_fwd(N, S, C_, dev, x=None, seed=21, arena=None):
     from van_gan_amd import ops
     g = torch.Generator(device=dev).manual_seed(seed)
     if x is None:
@@ -126,7 +153,9 @@ def _stem_fwd(N, S, C_, dev, x=None, seed=21):
     w = torch.randn(C_, generator=g, device=dev) * 0.4
     w[3] = 0.01
     gam, bet = torch.rand(C_, generator=g, device=dev) + 0.5, torch.randn(C_, generator=g, device=dev) * 0.1
-    sc, sh = torch.zeros(N, C_, device=dev), torch.zeros(N, C_, device=dev)
+    sc, sh = (LR.dev_out(arena, (N, C_), torch.float32, dev, 0.0, k, must_write=True) for k in ('scale', 'shift'))
+    if arena is not None:               # the kernel's own partial sums stay in the ops.Arena it takes them from
+        x, w, gam, bet = arena.put(x, name='x'), arena.put(w, name='w'), arena.put(gam, name='gamma'), arena.put(bet, name='beta')
     ar = ops.Arena(64 << 20, dev)
     ops.stem_short_fwd(ar, x, N, C_, w, gam, bet, sc, sh, round16=True)
     torch.cuda.synchronize()
@@ -139,10 +168,12 @@ def _stem_fwd(N, S, C_, dev, x=None, seed=21):
     ref_sh = bet.double()[None] - ref_sc * mu[:, None]
     err = dict(scale=LR.rel_l2(sc, ref_sc), shift=LR.rel_l2(sh, ref_sh))
     assert err['scale'] <= 1e-5 and err['shift'] <= 1e-5, err
+    if arena is not None:
+        arena.verify()
     return err
 
 
-def _stem_bwd(N, S, C_, dev, seed=22):
+def _stem_bwd(N, S, C_, dev, seed=22, arena=None):
     """vg_stem_short_bwd (d/dw, d/dgamma, d/dbeta of  IN(w x + b)  in two moments) against float64 autograd of the same expression."""
     from van_gan_amd import ops
     g = torch.Generator(device=dev).manual_seed(seed)
@@ -150,7 +181,9 @@ def _stem_bwd(N, S, C_, dev, seed=22):
     gy = torch.randn(N, S, C_, generator=g, device=dev).to(torch.bfloat16)
     w = torch.randn(C_, generator=g, device=dev) * 0.4
     gam = torch.rand(C_, generator=g, device=dev) + 0.5
-    dw, dgam, dbet = torch.zeros(C_, device=dev), torch.zeros(C_, device=dev), torch.zeros(C_, device=dev)
+    dw, dgam, dbet = (LR.dev_out(arena, (C_,), torch.float32, dev, 0.0, k) for k in ('dw', 'dgamma', 'dbeta'))
+    if arena is not None:
+        x, gy, w, gam = arena.put(x, name='x'), arena.put(gy, name='gy'), arena.put(w, name='w'), arena.put(gam, name='gamma')
     ar = ops.Arena(64 << 20, dev)
     ops.stem_short_bwd(ar, gy, x, N, C_, w, gam, dw, dgam, dbet, round16=True)
     torch.cuda.synchronize()
@@ -164,39 +197,53 @@ def _stem_bwd(N, S, C_, dev, seed=22):
     (out * gy.double()).sum().backward()
     err = dict(dw=LR.rel_l2(dw, wr.grad), dgamma=LR.rel_l2(dgam, gr.grad), dbeta=LR.rel_l2(dbet, br.grad))
     assert max(err.values()) <= 1e-4, err
+    if arena is not None:
+        arena.verify()
     return err
 
 
+def _flat_arena(nbytes, slots, dev):
+    """A guarded arena for `slots` tensors of `nbytes` bytes together."""
+    return guarded.GuardedArena(nbytes + slots * guarded.slot_cost(0), dev)
+
+
 def run_case(c, cid, dev):
-    """One case of call_recipes.cases_of on the device (tests/test_gpu_ragged.py runs its own list through here too)."""
+    """One case of call_recipes.cases_of on the device (tests/test_gpu_ragged.py and tests/test_gpu_batch3.py run their own lists through
+    here too), inside a guarded arena (tests/guarded.py): the parity assertions of the case, then every guard intact and every input
+    unchanged."""
     from van_gan_amd import ops
     kind = c['kind']
     if kind == 'anb':
-        err = CR.run_anb(dict(c['regime']), dev, name=cid)
+        r = dict(c['regime'])
+        err = CR.run_anb(r, dev, name=cid, arena=guarded.GuardedArena(CR.anb_bytes(r), dev))
     elif kind == 'apply2':
-        err = CR.run_apply2(dict(c['regime'][0][1]), dict(c['regime'][1][1]), dev, name=cid)
+        r1, r2 = dict(c['regime'][0][1]), dict(c['regime'][1][1])
+        err = CR.run_apply2(r1, r2, dev, name=cid, arena=guarded.GuardedArena(CR.anb_bytes(r1) + CR.anb_bytes(r2), dev))
     elif kind == 'decoder':
-        err = _decoder(c['block'], dev)
+        err = _decoder(c['block'], dev, arena=guarded.GuardedArena(_decoder_bytes(c['block']), dev))
     elif kind == 'fin':
-        err = dict(fin=CR.run_fin(c['recipe'], c['variant'], dev))
+        err = dict(fin=CR.run_fin(c['recipe'], c['variant'], dev, arena=LR.guarded_for(c['recipe'], dev)))
     elif kind == 'stem_short_fwd':
         r = dict(c['regime'])
         assert r['G'] == int(ops.lib.vg_stem_short_fwd_workgroups(r['N'], r['S']))
-        err = _stem_fwd(r['N'], r['S'], r['C'], dev)
+        err = _stem_fwd(r['N'], r['S'], r['C'], dev, arena=_flat_arena(4 * r['N'] * r['S'] + 64 * r['N'] * r['C'], 8, dev))
     elif kind == 'stem_short_bwd':
         r = dict(c['regime'])
         assert r['G'] == int(ops.lib.vg_stem_short_bwd_workgroups(r['N'], r['S'], r['C']))
-        err = _stem_bwd(r['N'], r['S'], r['C'], dev)
+        err = _stem_bwd(r['N'], r['S'], r['C'], dev, arena=_flat_arena(4 * r['N'] * r['S'] * (1 + r['C']), 8, dev))
     else:
         assert kind == 'tanh_bwd'
         n = dict(c['regime'])['n']
+        ga = _flat_arena(12 * n, 3, dev)
         g = torch.Generator(device=dev).manual_seed(23)
         y, dy = torch.tanh(torch.randn(n, generator=g, device=dev) * 2), torch.randn(n, generator=g, device=dev)
-        dp = torch.full((n,), float('nan'), device=dev)
+        y, dy = ga.put(y, name='y'), ga.put(dy, name='dy')
+        dp = ga.out((n,), torch.float32, None, name='dpre')           # 0xFF bytes: NaN, as before
         ops.tanh_bwd(dy, y, dp)
         torch.cuda.synchronize()
         err = dict(dpre=LR.rel_l2(dp, dy.double() * (1 - y.double() ** 2)))
         assert err['dpre'] <= 1e-6
+        ga.verify()
     _report(cid, err)
     return err
 
@@ -209,7 +256,7 @@ def test_recorded_call_matches_float64(cid):
 @pytest.mark.parametrize('fam', sorted(CR.fin_stress_cases()))
 def test_finalisation_tail_under_load(fam):
     c = CR.fin_stress_cases()[fam]
-    w = CR.stress_fin(c['recipe'], c['variant'], _dev(), launches=200)
+    w = CR.stress_fin(c['recipe'], c['variant'], _dev(), launches=200, arena=LR.guarded_for(c['recipe'], _dev()))
     _report('fin under load %s %s' % (fam, c['variant']), dict(worst=w))
 
 
@@ -239,7 +286,7 @@ _ANB_EXTRA = {
 
 @pytest.mark.parametrize('name', sorted(_ANB_EXTRA))
 def test_instance_norm_backward_edges(name):
-    err = CR.run_anb(_ANB_EXTRA[name], _dev(), seed=3, name=name)
+    err = CR.run_anb(_ANB_EXTRA[name], _dev(), seed=3, name=name, arena=guarded.GuardedArena(CR.anb_bytes(_ANB_EXTRA[name]), _dev()))
     _report('anb ' + name, err)
 
 
@@ -247,7 +294,7 @@ def test_apply2_jobs_of_different_grids():
     """The two jobs of one apply2 launch with different grids (job 2 strides by its own workgroup count)."""
     r1 = _anb(N=2, D=40, H=24, W=16, C=32, g_padded=0, act=0)
     r2 = _anb(N=2, D=40, H=24, W=16, C=96, g_padded=1)
-    err = CR.run_apply2(r1, r2, _dev(), seed=4, name='apply2 C32 + C96')
+    err = CR.run_apply2(r1, r2, _dev(), seed=4, name='apply2 C32 + C96', arena=guarded.GuardedArena(CR.anb_bytes(r1) + CR.anb_bytes(r2), _dev()))
     _report('apply2 C32 unpadded + C96 padded', err)
 
 
@@ -267,7 +314,9 @@ def test_in_finalize_two_sources_and_mult():
     sums1[..., 1] = sums1[..., 1] * 500 + 300
     gam, bet = torch.rand(c0 + c1, generator=g, device=dev) + 0.5, torch.randn(c0 + c1, generator=g, device=dev) * 0.2
     mult = (torch.rand(N, c0 + c1, generator=g, device=dev) > 0.3).float() * 2.0
-    out = [torch.full((N, c0 + c1), float('nan'), device=dev) for _ in range(4)]
+    ga = _flat_arena(1 << 20, 9, dev)                 # operands sealed, the four outputs 0xFF bytes (NaN, as before)
+    sums0, sums1, gam, bet, mult = (ga.put(t, name=k) for k, t in (('sums0', sums0), ('sums1', sums1), ('gamma', gam), ('beta', bet), ('mult', mult)))
+    out = [ga.out((N, c0 + c1), torch.float32, None, name=k) for k in ('scale', 'shift', 'mean', 'rstd')]
     ops.in_finalize(sums0, c0, cnt0, gam, bet, N, *out, sums1=sums1, c1=c1, count1=cnt1, mult=mult)
     torch.cuda.synchronize()
     s = torch.cat([sums0.double().sum(0) / cnt0, sums1.double().sum(0) / cnt1], dim=1)
@@ -278,6 +327,7 @@ def test_in_finalize_two_sources_and_mult():
     err = {k: LR.rel_l2(o, r) for k, o, r in zip(('scale', 'shift', 'mean', 'rstd'), out, ref)}
     _report('in_finalize two sources + mult', err)
     assert max(err.values()) <= 1e-5, err
+    ga.verify()
 
 
 @pytest.mark.parametrize('dims,C_,act,f32', [((32, 32, 32), 256, 0, False), ((32, 32, 32), 256, 1, False), ((64, 64, 64), 128, 1, False),
@@ -289,9 +339,10 @@ def test_affine_add_at_resnet_shapes(dims, C_, act, f32):
     g = torch.Generator(device=dev).manual_seed(32)
     N, S = 1, math.prod(dims)
     dt = torch.float32 if f32 else torch.bfloat16
-    a, b = torch.randn(N, S, C_, generator=g, device=dev).to(dt), torch.randn(N, S, C_, generator=g, device=dev).to(dt)
-    sa, ha, sb, hb = [torch.randn(N, C_, generator=g, device=dev) for _ in range(4)]
-    out = torch.full((N, S, C_), float('nan'), dtype=dt, device=dev)
+    ga = _flat_arena(3 * 4 * N * S * C_ + (1 << 20), 7, dev)
+    a, b = ga.put(torch.randn(N, S, C_, generator=g, device=dev).to(dt), name='a'), ga.put(torch.randn(N, S, C_, generator=g, device=dev).to(dt), name='b')
+    sa, ha, sb, hb = [ga.put(torch.randn(N, C_, generator=g, device=dev), name=k) for k in ('sa', 'ha', 'sb', 'hb')]
+    out = ga.out((N, S, C_), dt, None, name='out')                    # 0xFF bytes: NaN, as before
     ops.affine_add(a, sa, ha, act, b, sb, hb, N, S, C_, out)
     torch.cuda.synchronize()
     pa = a.double() * sa.double().view(N, 1, C_) + ha.double().view(N, 1, C_)
@@ -300,6 +351,7 @@ def test_affine_add_at_resnet_shapes(dims, C_, act, f32):
         assert LR.rel_l2(out, ref) <= 1e-6
     else:
         LR.close_bf16(out, ref, 'affine_add')
+    ga.verify()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -315,7 +367,7 @@ def test_stem_shortcut_on_a_near_constant_volume(kind):
     x = torch.ones(N, S, 1, device=dev)
     if kind != 'constant':
         x = x + 1e-3 * torch.randn(N, S, 1, generator=g, device=dev)
-    err = _stem_fwd(N, S, 16, dev, x=x)
+    err = _stem_fwd(N, S, 16, dev, x=x, arena=_flat_arena(4 * N * S + 64 * N * 16, 8, dev))
     _report('stem_short_fwd ' + kind, err)
 
 
@@ -347,7 +399,9 @@ def _ssim_ref(t, p):
 def test_loss_chain_at_config_shapes(cfg):
     """min-max (two ties of the min and of the max further apart than the reduction grid, so the tie counts add across workgroups; an odd
     S puts samples 1 and 2 on unaligned starts and their extrema in the scalar tail) -> BCE (p exactly 0 and 1 at the arg-extrema: clipped,
-    zero gradient) -> min-max backward; MSE, MSE against a constant on bf16 logits; SSIM loss and gradient (faces and edges included)."""
+    zero gradient) -> min-max backward; MSE, MSE against a constant on bf16 logits; SSIM loss and gradient (faces and edges included).
+    Every device tensor is a slot of a guarded arena (tests/guarded.py), filled as before (zeros stay zeros, NaN is 0xFF bytes): after
+    each group of launches every guard intact and every input unchanged."""
     from oracle import vangan_oracle as O
     from van_gan_amd import ops
     dev = _dev()
@@ -360,15 +414,18 @@ def test_loss_chain_at_config_shapes(cfg):
         far = (S - 1, 5) if (b >= 1 and S % 4) else (3, S - 700)              # samples >= 1 of an odd S: extrema in the scalar tail
         x[b, far[0]] = hi; x[b, far[1]] = hi
         x[b, S // 2 + 1] = lo; x[b, S - 2 if b >= 1 else 1] = lo
-    x = x.view(B, D, H, W, 1).contiguous()
-    t = (torch.rand(B, D, H, W, 1, generator=g, device=dev) > 0.7).float()
-    mm, y = torch.zeros(B, 4, device=dev), torch.zeros(B, D, H, W, 1, device=dev)
+    ga = _flat_arena(24 * 4 * B * S, 32, dev)
+    vol = (B, D, H, W, 1)
+    zeros = lambda shape, name: ga.out(shape, torch.float32, 0.0, name=name)
+    x = ga.put(x.view(vol).contiguous(), name='x')
+    t = ga.put((torch.rand(vol, generator=g, device=dev) > 0.7).float(), name='t')
+    mm, y = zeros((B, 4), 'mm'), zeros(vol, 'y')
     ops.minmax(x, B, S, mm)
     ops.minmax_apply(x, mm, B, S, y)
-    acc = torch.zeros(8, device=dev)
-    gy = torch.zeros_like(y)
+    acc = zeros((8,), 'acc')
+    gy = zeros(vol, 'gy')
     ops.bce(t, y, acc[0:1], 0.37, gy)
-    dx, tmp2 = torch.zeros_like(y), torch.zeros(B, 2, device=dev)
+    dx, tmp2 = zeros(vol, 'dx'), zeros((B, 2), 'tmp2')
     ops.minmax_bwd(x, y, gy, mm, B, S, tmp2, dx)
     torch.cuda.synchronize()
     assert mm[:, 2].tolist() == [2.0] * B and mm[:, 3].tolist() == [2.0] * B, mm       # tie counts
@@ -380,25 +437,28 @@ def test_loss_chain_at_config_shapes(cfg):
     assert float(y.min()) == 0.0 and float(y.max()) == 1.0
     assert err['minmax'] <= 1e-6 and err['bce'] <= 1e-4, err
     assert err['minmax_bwd'] <= 5e-3, err           # the bound the 480-voxel case meets (tests/test_gpu_ops.py)
+    ga.verify()
     del xr, yr
     # MSE and the LSGAN constant
-    a, b_ = torch.randn(B, S, generator=g, device=dev), torch.randn(B, S, generator=g, device=dev)
-    gb = torch.full((B, S), float('nan'), device=dev)
+    a, b_ = ga.put(torch.randn(B, S, generator=g, device=dev), name='a'), ga.put(torch.randn(B, S, generator=g, device=dev), name='b')
+    gb = ga.out((B, S), torch.float32, None, name='gb')                 # 0xFF bytes: NaN
     ops.mse(a, b_, acc[1:2], 0.5, gb)
-    bl = b_.to(torch.bfloat16)
-    gx = torch.full((B, S), float('nan'), device=dev)
+    bl = ga.put(b_.to(torch.bfloat16), name='b (bf16)')
+    gx = ga.out((B, S), torch.float32, None, name='gx')
     ops.mse_const(bl, 1.0, acc[2:3], 2.0, gx)
     torch.cuda.synchronize()
+    ga.verify()
     ad, bd, bld = a.double(), b_.double(), bl.double()
     err.update(mse=_sum_err(acc[1], ((ad - bd) ** 2).sum()), mse_grad=LR.rel_l2(gb, 0.5 * 2 * (bd - ad)),
                mse_const=_sum_err(acc[2], ((bld - 1) ** 2).sum()), mse_const_grad=LR.rel_l2(gx, 4 * (bld - 1)))
     assert err['mse'] <= 1e-4 and err['mse_const'] <= 1e-4 and err['mse_grad'] <= 1e-5 and err['mse_const_grad'] <= 1e-5, err
     # SSIM
-    p, tt = torch.rand(B, D, H, W, 1, generator=g, device=dev), torch.rand(B, D, H, W, 1, generator=g, device=dev)
-    part, gp = torch.zeros(3, B, D, H, W, 1, device=dev), torch.zeros(B, D, H, W, 1, device=dev)
+    p, tt = ga.put(torch.rand(vol, generator=g, device=dev), name='p'), ga.put(torch.rand(vol, generator=g, device=dev), name='tt')
+    part, gp = zeros((3,) + vol, 'part'), zeros(vol, 'gp')
     ops.ssim_fwd(tt, p, (B, D, H, W), acc[3:4], part)
     ops.ssim_bwd(tt, p, part, (B, D, H, W), 1.0, gp)
     torch.cuda.synchronize()
+    ga.verify()
     ls, gref = _ssim_ref(tt, p)
     gref = gref.to(dev)
     err['ssim'] = _sum_err(acc[3], ls)
@@ -413,7 +473,9 @@ def test_loss_chain_at_config_shapes(cfg):
 @pytest.mark.parametrize('cfg', ['128^3 B1', '64^3 B2', '128x128x64 B2', '32^3 B1', '32^3 B3'])
 def test_skeleton_and_cldice_at_config_shapes(cfg):
     """soft skeleton (15 iterations, with and without the aux codes) -> dot_sums -> clDice coefficients and gradients, against float64
-    autograd through the oracle on continuous data; and an all-zero target (empty skeleton: only the smooth terms)."""
+    autograd through the oracle on continuous data; and an all-zero target (empty skeleton: only the smooth terms).
+    Every device tensor of the launches is a slot of a guarded arena (tests/guarded.py), filled as before; guards and inputs are verified
+    after the launches of each target."""
     from oracle import vangan_oracle as O
     from van_gan_amd import ops
     dev = _dev()
@@ -425,24 +487,33 @@ def test_skeleton_and_cldice_at_config_shapes(cfg):
     p = torch.rand(vol, generator=g, device=dev)
     t_ = (F.avg_pool3d(torch.rand(B, 1, D, H, W, generator=g, device=dev), 3, 1, 1) > 0.52).float().permute(0, 2, 3, 4, 1).contiguous()
     for empty in (False, True):
-        t = torch.zeros_like(t_) if empty else t_
-        imgs_p, skels_p = torch.zeros((it + 2,) + vol, device=dev), torch.zeros((it + 1,) + vol, device=dev)
-        imgs_t, skels_t = torch.zeros((it + 2,) + vol, device=dev), torch.zeros((it + 1,) + vol, device=dev)
-        aux = torch.zeros(ops.skel_aux_bytes((B, D, H, W), it), dtype=torch.uint8, device=dev)
-        ops.soft_skel_fwd(p, (B, D, H, W), it, imgs_p, skels_p, aux)
+        nv = B * D * H * W
+        n_aux = ops.skel_aux_bytes((B, D, H, W), it)
+        ga = _flat_arena(4 * nv * (2 * (2 * it + 3) + 7 + 6) + n_aux, 24, dev)
+        zeros = lambda shape, name: ga.out(shape, torch.float32, 0.0, name=name)
+        t = ga.put(torch.zeros_like(t_) if empty else t_, name='t')
+        pa = ga.put(p, name='p')
+        imgs_p, skels_p = zeros((it + 2,) + vol, 'imgs_p'), zeros((it + 1,) + vol, 'skels_p')
+        imgs_t, skels_t = zeros((it + 2,) + vol, 'imgs_t'), zeros((it + 1,) + vol, 'skels_t')
+        aux = ga.out((n_aux,), torch.uint8, 0, name='aux')
+        ops.soft_skel_fwd(pa, (B, D, H, W), it, imgs_p, skels_p, aux)
         ops.soft_skel_fwd(t, (B, D, H, W), it, imgs_t, skels_t)
-        sums, coef = torch.zeros(9, device=dev), torch.zeros(8, device=dev)
-        ops.dot_sums(skels_p[it], t, sums[0:3]); ops.dot_sums(skels_t[it], p, sums[3:6]); ops.dot_sums(t, p, sums[6:9])
+        sums, coef = zeros((9,), 'sums'), zeros((8,), 'coef')
+        ops.dot_sums(skels_p[it], t, sums[0:3]); ops.dot_sums(skels_t[it], pa, sums[3:6]); ops.dot_sums(t, pa, sums[6:9])
         w = 5.0
         ops.cldice_coef(sums, w, 0.5, coef)
-        gskel, gp = torch.zeros(vol, device=dev), torch.zeros(vol, device=dev)
+        gskel, gp = zeros(vol, 'gskel'), zeros(vol, 'gp')
         ops.cldice_grads(t, skels_t[it], coef, gskel, gp)
-        gp0 = gp.clone()
-        work = torch.full((4,) + vol, float('nan'), device=dev)
+        torch.cuda.synchronize()
+        for k in (imgs_p, skels_p, imgs_t, skels_t, aux, coef, gskel):            # written above, only read from here on
+            ga.seal(k)
+        gp0 = ga.put(gp, name='gp0', mutable=True)
+        work = ga.out((4,) + vol, torch.float32, None, name='work')              # 0xFF bytes: NaN
         ops.soft_skel_bwd(imgs_p, skels_p, gskel, (B, D, H, W), it, work, gp, aux)
-        work3 = torch.zeros((3,) + vol, device=dev)
+        work3 = zeros((3,) + vol, 'work3')
         ops.soft_skel_bwd(imgs_p, skels_p, gskel, (B, D, H, W), it, work3, gp0)
         torch.cuda.synchronize()
+        ga.verify()
         pr = p.double().requires_grad_(True)
         sk_p = O.soft_skel(pr[..., 0], it)
         sk_t = O.soft_skel(t.double()[..., 0], it)
@@ -474,6 +545,12 @@ def test_adam_over_the_real_tables(net):
     dev = _dev()
     specs = {'gen': gen_param_specs, 'disc': disc_param_specs, 'resnet': resnet_param_specs}[net]()
     st = ParamStore(specs, dev)
+    # the store's tables as slots of a guarded arena (tests/guarded.py): weights, gradients, both Adam slots, the segment table and the
+    # norms[T + 2 * ceil(total / 4096)] block at exactly its documented length
+    assert st.norms.numel() == st.T + 2 * ((st.total + 4095) // 4096)
+    ga = _flat_arena(16 * st.total + 8 * (st.T + 1) + 4 * st.norms.numel(), 8, dev)
+    st.w, st.g, st.m, st.v = (ga.out((st.total,), torch.float32, 0.0, name=k) for k in ('w', 'g', 'm', 'v'))
+    st.seg_off, st.norms = ga.put(st.seg_off, name='seg_off'), ga.out((st.norms.numel(),), torch.float32, 0.0, name='norms')
     off = st.seg_off.cpu().tolist()
     assert any(o % 4096 for o in off[1:-1]) and any((a // 4096) != ((b - 1) // 4096) for a, b in zip(off[:-1], off[1:]))
     assert net != 'disc' or any(o % 4096 == 0 for o in off[1:-1])        # spans inside, across and (disc) at the start of tensors
@@ -513,3 +590,4 @@ def test_adam_over_the_real_tables(net):
     w_dev = run(True)
     assert torch.equal(w_dev, w_host), 'adam_clip_dev (rate from device memory) differs from adam_clip'
     assert torch.equal(run(False), w_host), 'not reproducible bit for bit'
+    ga.verify()

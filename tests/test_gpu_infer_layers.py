@@ -58,7 +58,7 @@ def _report(name, err):
 # ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('kv', _NEW, ids=[_id(kv) for kv in _NEW])
 def test_inference_only_variant_matches_oracle(kv):
-    err = LR.run_recipe(_REPS[kv]['recipe'], kv[1], _dev())
+    err = LR.run_recipe(_REPS[kv]['recipe'], kv[1], _dev(), arena=LR.guarded_for(_REPS[kv]['recipe'], _dev()))
     _report('bf16 ' + _id(kv), err)
 
 
@@ -73,13 +73,13 @@ def test_inference_ksplit_case_exists():
 def test_inference_ksplit_exchange_is_bitwise_stable_under_load(kv):
     """enc4.cb1 / enc4.cb2 / bridge.cb1 / bridge.cb2 of the two-window batch: four K slices exchange partial tiles through the per-stream
     scratch (tests/test_gpu_layers.py has the argument).  200 launches on two streams must reproduce the first bit for bit."""
-    LR.stress_recipe(_REPS[kv]['recipe'], kv[1], _dev(), launches=200)
+    LR.stress_recipe(_REPS[kv]['recipe'], kv[1], _dev(), launches=200, arena=LR.guarded_for(_REPS[kv]['recipe'], _dev()))
 
 
 @pytest.mark.parametrize('cid', sorted(_FIN))
 def test_inference_finalisation_tail_matches_float64(cid):
     c = _FIN[cid]
-    _report(cid, dict(fin=CR.run_fin(c['recipe'], c['variant'], _dev())))
+    _report(cid, dict(fin=CR.run_fin(c['recipe'], c['variant'], _dev(), arena=LR.guarded_for(c['recipe'], _dev()))))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -93,7 +93,7 @@ def test_fp16_build_layer_variant_matches_oracle(kv):
     from van_gan_amd import ops
     with ops.Fp16():
         assert ops.lib.vg_storage16() == 1
-        err = LR.run_recipe(_REPS[kv]['recipe'], kv[1], _dev(), storage=torch.float16)
+        err = LR.run_recipe(_REPS[kv]['recipe'], kv[1], _dev(), storage=torch.float16, arena=LR.guarded_for(_REPS[kv]['recipe'], _dev()))
     _report('fp16 ' + _id(kv), err)
 
 
@@ -160,12 +160,14 @@ def test_storage_conversions_are_bitwise_rne(storage):
     x = torch.cat([_special_values(), rnd, torch.randn(3, generator=g)])
     n = x.numel()
     assert n % 8 != 0 and abs(n - (1 << 20)) < (1 << 14)
-    xd = x.to(dev)
-    y = torch.full((n + 8,), 1.0, dtype=storage, device=dev)                  # 8 guard elements behind the end
+    import guarded
+    ga = guarded.GuardedArena(16 * (n + (1 << 17)) + 4 * guarded.slot_cost(0), dev)     # inputs sealed; outputs keep their 8 guard elements too
+    xd = ga.put(x, name='x')
+    y = ga.out((n + 8,), storage, 1.0, name='y')                              # 8 guard elements behind the end
     want = x.to(storage)                                                      # CPU: IEEE round to nearest even
     patterns = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(storage)        # every 16-bit pattern
-    back_in = torch.cat([patterns, want]).to(dev)
-    back = torch.full((back_in.numel() + 8,), 7.0, dtype=torch.float32, device=dev)
+    back_in = ga.put(torch.cat([patterns, want]), name='back_in')
+    back = ga.out((back_in.numel() + 8,), torch.float32, 7.0, name='back')
     ctx = ops.Fp16() if storage == torch.float16 else None
     if ctx is not None:
         ctx.__enter__()
@@ -183,6 +185,7 @@ def test_storage_conversions_are_bitwise_rne(storage):
     gn, wn = torch.isnan(bg), torch.isnan(bw)
     assert torch.equal(gn, wn)
     assert torch.equal(bg.view(torch.int32)[~wn], bw.view(torch.int32)[~wn]), '16 bit -> f32 is exact'
+    ga.verify()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -252,7 +255,10 @@ def test_fp16_build_stem_shortcut_scale_and_shift():
     w = torch.randn(C_, generator=g, device=dev) * 0.4
     w[3] = 0.01
     gam, bet = torch.rand(C_, generator=g, device=dev) + 0.5, torch.randn(C_, generator=g, device=dev) * 0.1
-    sc, sh = torch.zeros(N, C_, device=dev), torch.zeros(N, C_, device=dev)
+    import guarded
+    ga = guarded.GuardedArena(4 * N * S + (1 << 20) + 6 * guarded.slot_cost(0), dev)
+    x, w, gam, bet = ga.put(x, name='x'), ga.put(w, name='w'), ga.put(gam, name='gamma'), ga.put(bet, name='beta')
+    sc, sh = ga.out((N, C_), torch.float32, None, name='scale'), ga.out((N, C_), torch.float32, None, name='shift')
     with ops.Fp16():
         ar = ops.Arena(64 << 20, dev)
         ops.stem_short_fwd(ar, x, N, C_, w, gam, bet, sc, sh, round16=True)
@@ -270,3 +276,4 @@ def test_fp16_build_stem_shortcut_scale_and_shift():
     assert err['scale'] <= 1e-5 and err['shift'] <= 1e-5, err
     other = restate(w.bfloat16().double())                            # the check tells the two roundings apart
     assert LR.rel_l2(other[0], ref_sc) > 1e-4
+    ga.verify()

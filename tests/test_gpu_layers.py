@@ -2,7 +2,8 @@
 ones), each a real layer call of the train step -- forward with its on-read InstanceNorm/activation, virtual upsample+concat,
 noise, residual and statistics epilogue; data gradient on the padded grid; weight + bias gradient -- replayed with random
 contents and compared with the oracle's convolution / autograd on the same bf16-rounded operands
-(tests/layer_recipes.py; tolerances of tests/test_gpu_ops.py)."""
+(tests/layer_recipes.py; tolerances of tests/test_gpu_ops.py).  Every replay runs inside a guarded arena (tests/guarded.py): operands
+with NaN neighbours, outputs that start as NaN, and after the parity assertions every guard byte intact and every input unchanged."""
 import pytest
 import torch
 
@@ -22,7 +23,8 @@ def _id(kv):
 @pytest.mark.parametrize('kv', _KEYS, ids=[_id(kv) for kv in _KEYS])
 def test_layer_variant_matches_oracle(kv):
     r = _REPS[kv]
-    LR.run_recipe(r['recipe'], kv[1], torch.device('cuda:0'))
+    dev = torch.device('cuda:0')
+    LR.run_recipe(r['recipe'], kv[1], dev, arena=LR.guarded_for(r['recipe'], dev))       # parity, then guards intact and inputs unchanged
 
 
 
@@ -41,4 +43,5 @@ def test_ksplit_exchange_is_bitwise_stable_under_load(kv):
     last arriver reads with agent-scope loads and resets the counter; DESIGN 3.1 has the hardware argument) has no fence.  200
     launches of every K-split variant of both families, alternating between two streams, must reproduce the first launch bit for bit."""
     r = _REPS[kv]
-    LR.stress_recipe(r['recipe'], kv[1], torch.device('cuda:0'), launches=200)
+    dev = torch.device('cuda:0')
+    LR.stress_recipe(r['recipe'], kv[1], dev, launches=200, arena=LR.guarded_for(r['recipe'], dev))

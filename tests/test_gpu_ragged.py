@@ -68,7 +68,7 @@ def _report(name, err):
 @pytest.mark.parametrize('kv', _KEYS, ids=[_id(kv) for kv in _KEYS])
 def test_ragged_variant_matches_oracle(kv):
     """run_recipe asserts that the dry run of the rebuilt call selects exactly kv[1] before it launches."""
-    err = LR.run_recipe(_REPS[kv]['recipe'], kv[1], _dev())
+    err = LR.run_recipe(_REPS[kv]['recipe'], kv[1], _dev(), arena=LR.guarded_for(_REPS[kv]['recipe'], _dev()))
     _report('bf16 ' + _id(kv), err)
 
 
@@ -77,7 +77,7 @@ def test_fp16_build_ragged_inference_variant_matches_oracle(kv):
     from van_gan_amd import ops
     with ops.Fp16():
         assert ops.lib.vg_storage16() == 1
-        err = LR.run_recipe(_IREPS[kv]['recipe'], kv[1], _dev(), storage=torch.float16)
+        err = LR.run_recipe(_IREPS[kv]['recipe'], kv[1], _dev(), storage=torch.float16, arena=LR.guarded_for(_IREPS[kv]['recipe'], _dev()))
     _report('fp16 ' + _id(kv, _IREPS), err)
 
 
@@ -92,13 +92,13 @@ _KSPLIT_FIN = [cid for cid in _CIDS if _CASES[cid]['kind'] == 'fin' and ('fwd', 
 def test_ragged_ksplit_exchange_is_bitwise_stable_under_load(kv):
     """The K slices' partial tiles of a ragged grid's last, partly masked tile go through the same per-stream scratch: 200 launches on two
     streams must reproduce the first bit for bit (tests/test_gpu_layers.py has the argument)."""
-    LR.stress_recipe(_REPS[kv]['recipe'], kv[1], _dev(), launches=200)
+    LR.stress_recipe(_REPS[kv]['recipe'], kv[1], _dev(), launches=200, arena=LR.guarded_for(_REPS[kv]['recipe'], _dev()))
 
 
 @pytest.mark.parametrize('cid', _KSPLIT_FIN)
 def test_ragged_ksplit_finalisation_tail_under_load(cid):
     c = _CASES[cid]
-    w = CR.stress_fin(c['recipe'], c['variant'], _dev(), launches=200)
+    w = CR.stress_fin(c['recipe'], c['variant'], _dev(), launches=200, arena=LR.guarded_for(c['recipe'], _dev()))
     _report('fin under load ' + cid, dict(worst=w))
 
 
